@@ -10,9 +10,13 @@ default law), inputs/targets from the same generator with rank-dependent seeds (
 N > 1: one process per GPU (torchrun), gradients all-reduced over RCCL in four buckets
 overlapped with the staged backward; weak scaling (8 images per GPU).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
 
-Rank 0 prints ONE JSON line.  Extra objects: roofline of the dominant kernel family (kernel time
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the
+headline (value, ms_per_step, loss).  --dump-outputs DIR writes what the last timed step left
+(loss, updated parameters, gradients, BatchNorm running statistics) as DIR/<name>.npy; the
+weights, inputs, targets and dropout seeds are the same from run to run.  --full adds everything
+that takes runs of its own: roofline of the dominant kernel family (kernel time
 per launch from the committed rocprofv3 summary of this command, beside the live HIP-event time
 of its dispatches in the timed region; algorithmic bytes per SURVEY.md §8(d)),
 cpu_baseline (the oracle restatement timed on this host's cores on a bounded sample), and the
@@ -49,6 +53,12 @@ def parse():
     ap.add_argument("--width", type=int, default=2048)
     ap.add_argument("--classes", type=int, default=19)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the census / roofline / per-family figures, the step-time "
+                         "distribution, the forward-only, fp16 and published-configuration rates "
+                         "and the CPU baseline (the options below select among them)")
     ap.add_argument("--profile-kind", type=int, default=0, help="0 = dominant (census)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-forward", action="store_true")
@@ -59,7 +69,10 @@ def parse():
     ap.add_argument("--no-cfg5", action="store_true")
     ap.add_argument("--no-extra", action="store_true",
                     help="skip the fp16 train-step line and the published-configuration line")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def launch_ranks(n):
@@ -290,6 +303,46 @@ def published_config_rate(args, dev):
                       "loss.item() per step"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, loss, model):
+    """What a caller of the timed train step holds after its last step, as <path>/<name>.npy
+    (float32): the loss it returned, the updated parameters, their gradients and the BatchNorm
+    running statistics, each family concatenated in named_parameters() / named_buffers() order
+    (names.json lists every tensor's name and element range)."""
+    import numpy as np
+    import torch
+    params = list(model.named_parameters())
+    stats = [(k, v) for k, v in model.named_buffers() if v.is_floating_point()]
+
+    def flat(tensors):
+        return torch.cat([t.detach().float().reshape(-1) for t in tensors]).cpu().numpy()
+
+    arrays = {
+        "loss": loss.detach().float().reshape(1).cpu().numpy(),
+        "params": flat([p for _, p in params]),
+        "grads": flat([p.grad if p.grad is not None else torch.zeros_like(p) for _, p in params]),
+        "bn_running_stats": flat([v for _, v in stats]),
+    }
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    names = {}
+    for fam, items in (("params", params), ("bn_running_stats", stats)):
+        off, rows = 0, []
+        for k, v in items:
+            rows.append([k, off, off + v.numel()])
+            off += v.numel()
+        names[fam] = rows
+    names["grads"] = names["params"]
+    with open(os.path.join(path, "names.json"), "w") as fh:
+        json.dump(names, fh)
+
+
 def main():
     args = parse()
     env_world = os.environ.get("WORLD_SIZE")
@@ -334,6 +387,9 @@ def main():
     x = torch.from_numpy(portable_init.input_tensor(1 + rank, (B, 3, H, W))).to(dev).to(dt)
     t = torch.from_numpy(portable_init.target_tensor(3 + rank, (B, H, W), args.classes,
                                                      0.05)).to(dev)
+    # each train forward draws its dropout seed from torch's CPU generator: fix the sequence so
+    # that two runs with the same arguments compute the same steps
+    torch.manual_seed(0)
 
     def step():
         opt.zero_grad(set_to_none=True)
@@ -353,42 +409,45 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    loss = None
     for _ in range(args.warmup):
         loss = step()
     barrier()
-    first_loss = float(loss.item())
+    first_loss = float(loss.item()) if loss is not None else None
 
-    # census (untimed): which kernel family dominates the step
-    kind = args.profile_kind
+    # census (untimed, --full): which kernel family dominates the step
+    kind = args.profile_kind if args.full else 0
     census = {}
-    if kind == 0:
+    if args.full and kind == 0:
         for k, name in PROF_KINDS.items():
             ms, n, b, f = prof(lib, k, step, 4096)
             census[name] = round(ms, 4)
         kind = max(PROF_KINDS, key=lambda k: census[PROF_KINDS[k]])
     barrier()
 
-    # ---- timed region: K steps; the dominant family's dispatches in the last tenth of the timed
-    # steps carry kernel-bound HIP events (hipExtLaunchKernelGGL: each event pair holds its
-    # dispatch's own start / end timestamps, the kernel time rocprofv3 reports; no marker
-    # packets on the stream); the events are created before the region
+    # ---- timed region: K steps; with --full the dominant family's dispatches in the last tenth
+    # of the timed steps carry kernel-bound HIP events (hipExtLaunchKernelGGL: each event pair
+    # holds its dispatch's own start / end timestamps, the kernel time rocprofv3 reports; no
+    # marker packets on the stream); the events are created before the region
     nprof = max(1, args.steps // 10)
-    _lib.check(lib.fscnn_prof_begin(kind, 512 * nprof), "fscnn_prof_begin")
     ms, n, b, f = (ctypes.c_double(), ctypes.c_longlong(), ctypes.c_double(), ctypes.c_double())
-    _lib.check(lib.fscnn_prof_end(ctypes.byref(ms), ctypes.byref(n), ctypes.byref(b),
-                                  ctypes.byref(f)), "fscnn_prof_end")
+    if args.full:
+        _lib.check(lib.fscnn_prof_begin(kind, 512 * nprof), "fscnn_prof_begin")
+        _lib.check(lib.fscnn_prof_end(ctypes.byref(ms), ctypes.byref(n), ctypes.byref(b),
+                                      ctypes.byref(f)), "fscnn_prof_end")
     barrier()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        if i == args.steps - nprof:
+        if args.full and i == args.steps - nprof:
             lib.fscnn_prof_begin(kind, 512 * nprof)
             if world > 1:
                 net.timing = True  # per-bucket all-reduce / exposed comm events (ddp.py)
         loss = step()
     barrier()
     elapsed = time.perf_counter() - t0
-    _lib.check(lib.fscnn_prof_end(ctypes.byref(ms), ctypes.byref(n), ctypes.byref(b),
-                                  ctypes.byref(f)), "fscnn_prof_end")
+    if args.full:
+        _lib.check(lib.fscnn_prof_end(ctypes.byref(ms), ctypes.byref(n), ctypes.byref(b),
+                                      ctypes.byref(f)), "fscnn_prof_end")
     last_loss = float(loss.item())
     per_rank_ms = [round(1e3 * elapsed / args.steps, 3)]
     if world > 1:
@@ -397,7 +456,39 @@ def main():
         dist.all_gather(allt, tt)
         per_rank_ms = [round(1e3 * float(v.item()) / args.steps, 3) for v in allt]
         elapsed = max(float(v.item()) for v in allt)
+    # what the last timed step left, before any further step moves the weights
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, model)
 
+    value = world * B * args.steps / elapsed
+    result = {
+        "metric": METRIC, "value": round(value, 2), "unit": "images/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": args.dtype,
+        "data": "synthetic (portable counter-based generator; random-init weights, default law)",
+        "config": {"workload": ("cfg3 train step: fwd + CE(ignore -1) + bwd + fused SGD" + (" (unfused CE)" if args.unfused_loss else " (fused low-res upsample+CE head)")),
+                   "model": "FastSCNN (19 classes)", "global_batch": world * B,
+                   "per_gpu_batch": B, "resolution": [H, W], "parallelism": "dp%d" % world},
+        "loss": {"after_warmup": None if first_loss is None else round(first_loss, 5),
+                 "final": round(last_loss, 5)},
+        "per_rank_ms_per_step": per_rank_ms,
+        "comm": {"backend": dist.get_backend() if world > 1 else None,
+                 "world_size": dist.get_world_size() if world > 1 else 1,
+                 "buckets": 4 if world > 1 else 0},
+    }
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:
+        return finish()
+
+    # ---- --full: everything below takes runs of its own
     # per-step distribution (BASELINE.md §2 asks for a median over >= 20 iterations): K more
     # steps AFTER the timed region, each bracketed by events on the caller's stream (one event per
     # step boundary; it idles the stream ~7 us, so these steps are not the ones `value` times)
@@ -428,7 +519,6 @@ def main():
         depthwise[pname]["_recs"] = res[4]
     barrier()
 
-    value = world * B * args.steps / elapsed
     avg_ms = ms.value / max(1, n.value)
     bytes_per_launch = b.value / max(1, n.value)
     flops_per_launch = f.value / max(1, n.value)
@@ -498,10 +588,7 @@ def main():
         except Exception:
             pass
 
-    result = {
-        "metric": METRIC, "value": round(value, 2), "unit": "images/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True,
+    result.update({
         "step_ms_distribution": {"median": round(median_ms, 3), "min": round(step_ms[0], 3),
                                  "max": round(step_ms[-1], 3), "n": len(step_ms),
                                  "timing": "HIP events per step boundary on the caller's stream, "
@@ -514,18 +601,8 @@ def main():
                                 "family's algorithmic bytes per step over its rocprofv3 kernel "
                                 "time per step (profiles/rocprof_family_<dtype>.json); dw_wgrad "
                                 "runs on the low-priority side stream beside the main stream"),
-        "scaling": "weak", "vs_baseline": None, "dtype": args.dtype,
-        "data": "synthetic (portable counter-based generator; random-init weights, default law)",
-        "config": {"workload": ("cfg3 train step: fwd + CE(ignore -1) + bwd + fused SGD" + (" (unfused CE)" if args.unfused_loss else " (fused low-res upsample+CE head)")),
-                   "model": "FastSCNN (19 classes)", "global_batch": world * B,
-                   "per_gpu_batch": B, "resolution": [H, W], "parallelism": "dp%d" % world},
         "roofline": roof,
-        "loss": {"after_warmup": round(first_loss, 5), "final": round(last_loss, 5)},
-        "per_rank_ms_per_step": per_rank_ms,
-        "comm": {"backend": dist.get_backend() if world > 1 else None,
-                 "world_size": dist.get_world_size() if world > 1 else 1,
-                 "buckets": 4 if world > 1 else 0},
-    }
+    })
     if world > 1:
         net.timing = False
         cs = net.comm_stats()
@@ -606,11 +683,7 @@ def main():
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args)
 
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

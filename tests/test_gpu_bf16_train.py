@@ -26,7 +26,7 @@ fused Dropout / BN-backward epilogue is covered against the oracle, not only aga
   * every gradient tensor within 1.5x that budget, median ratio <= 1.0;
   * whole-vector cosine to fp64 >= the worst realisation's - 0.02 (and that one >= 0.95);
   * the loss within 1.5x the largest realisation's loss error.
-Reference: /root/reference/train.py:269-275 (the AMP train step), SURVEY Appendix B.
+Reference: train.py:269-275 (the AMP train step), SURVEY Appendix B.
 """
 import numpy as np
 import pytest

@@ -28,5 +28,5 @@ LT=$(find $O/layers/tr -name '*kernel_trace.csv' | head -1)
 python3 tools/rocprof_layers.py table "$LT" $O/layers/scopes.json $O/layers.md > /dev/null || exit 1
 rm -f "$LT"
 grep -A16 "kernel family" $O/layers.md | head -40
-timeout -k 10 600 python -u bench.py > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 600 python -u bench.py --full > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 cat $O/bench.json

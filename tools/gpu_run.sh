@@ -13,7 +13,7 @@ if [[ $# -gt 0 ]]; then
   grep -E "PASSED|FAILED|ERROR|passed|failed|cosine|ratio|flips|loss:" gpurun_out/t_${TAG}.log | tail -40
   [[ $rc -eq 0 ]] || { echo "pytest rc=$rc: stopping"; exit $rc; }
 fi
-timeout -k 10 300 python -u bench.py --no-cpu-baseline --no-extra --no-cfg5 \
+timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --no-extra --no-cfg5 \
     > gpurun_out/bench_${TAG}.json 2> gpurun_out/bench_${TAG}.err || { tail -20 gpurun_out/bench_${TAG}.err; exit 1; }
 python3 - gpurun_out/bench_${TAG}.json <<'PY'
 import json, sys

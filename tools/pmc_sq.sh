@@ -15,7 +15,7 @@ if [ -n "${PMC_EVAL:-}" ]; then
       python3 tools/fwd_run.py --cfg "$PMC_EVAL" --reps 2 > "$OUT/p.log" 2>&1
 else
   timeout -s KILL 300 rocprofv3 --pmc $CTRS --output-format csv -d "$OUT/p" -o run -- \
-      python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-forward --no-extra > "$OUT/p.log" 2>&1
+      python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-forward --no-extra > "$OUT/p.log" 2>&1
 fi
 python3 - "$OUT" "$PAT" <<'PY'
 import csv, glob, os, sys, collections
