@@ -39,6 +39,11 @@ SIGNATURES = {
                                c_int, c_int, c_vp]),
     "fscnn_normalize_u8": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp]),
     "fscnn_remap_labels": (c_int, [c_vp, c_ll, c_vp, c_int, c_int, c_ll, c_vp, c_vp]),
+    "fscnn_sync_tables": (c_int, [c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, P_int]),
+    "fscnn_sync_blur_weights": (c_int, [c_float, ctypes.POINTER(ctypes.c_uint),
+                                        ctypes.POINTER(ctypes.c_uint)]),
+    "fscnn_sync_transform": (c_int, [c_vp, c_vp, c_ll, c_int, c_int, c_vp, c_int, c_int, c_vp,
+                                     c_vp, c_vp, c_int, c_vp, c_vp, c_vp]),
     "fscnn_ohem_prob": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_ll, c_ll, c_float, c_vp, c_vp,
                                 c_vp]),
     "fscnn_ohem_threshold": (c_int, [c_vp, c_ll, c_vp, c_ll, c_float, c_vp, c_vp, c_vp]),

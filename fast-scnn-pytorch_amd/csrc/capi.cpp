@@ -426,6 +426,31 @@ int fscnn_remap_labels(const unsigned char* labels, long long n, const long long
   return remap_labels(labels, n, lut, lut_size, offset, invalid, out, S(stream));
 }
 
+int fscnn_sync_tables(int in_size, int out_size, int start, int count, int kmax, int* bounds,
+                      int* coef, int* nearest, int* ksize) {
+  return sync_tables(in_size, out_size, start, count, kmax, bounds, coef, nearest, ksize);
+}
+
+int fscnn_sync_blur_weights(float radius, unsigned* ww, unsigned* fw) {
+  return sync_blur_weights(radius, ww, fw);
+}
+
+int fscnn_sync_transform(const void* host_blob, const void* device_blob, long long blob_bytes,
+                         int N, int crop, const long long* lut, int lut_size, int lut_offset,
+                         const float* mean, const float* std, void* x, int out_dtype,
+                         long long* target, unsigned char* crop_u8, void* stream) {
+  if (!host_blob || !device_blob || !lut || !mean || !std || !x || !target) {
+    set_error("fscnn_sync_transform: null argument");
+    return E_INVALID;
+  }
+  if (out_dtype != DT_F32 && out_dtype != DT_BF16) {
+    set_error("fscnn_sync_transform: out_dtype %d", out_dtype);
+    return E_INVALID;
+  }
+  return sync_transform(host_blob, device_blob, blob_bytes, N, crop, lut, lut_size, lut_offset,
+                        mean, std, x, out_dtype, target, crop_u8, S(stream));
+}
+
 int fscnn_ohem_prob(const void* logits, int dtype, const long long* target, int N, int C,
                     long long HW, long long ignore_index, float thresh, float* prob,
                     unsigned long long* counts, void* stream) {

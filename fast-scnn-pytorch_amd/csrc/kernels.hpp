@@ -636,6 +636,15 @@ int normalize_u8(const uint8_t* x, int N, int H, int W, const float* mean, const
 // label-id -> train-id lookup (out-of-table ids -> invalid)
 int remap_labels(const uint8_t* in, long long n, const long long* lut, int lut_size, int offset,
                  long long invalid, long long* out, hipStream_t st);
+// GPU augmentation (augment.hip; host tables: sync_tables.cpp).  `hblob` / `dblob`: N
+// fscnn_sync_desc + their int32 tables in host / device memory (include/fastscnn.h)
+int sync_tables(int in_size, int out_size, int start, int count, int kmax, int* bounds, int* coef,
+                int* nearest, int* ksize_out);
+int sync_blur_weights(float radius, unsigned* ww_out, unsigned* fw_out);
+int sync_transform(const void* hblob, const void* dblob, long long blob_bytes, int N, int crop,
+                   const long long* lut, int lut_size, int lut_offset, const float* mean,
+                   const float* std, void* x, int out_dtype, long long* target, uint8_t* crop_u8,
+                   hipStream_t st);
 int im2col3(const Im2ColArgs& a, int dtype, hipStream_t st);
 int col2im3(const Col2ImArgs& a, int dtype, hipStream_t st);
 // *p = v (one thread): per-call scalars that captured graphs read from device memory

@@ -182,6 +182,47 @@ int fscnn_normalize_u8(const unsigned char* images, int N, int H, int W, const f
 int fscnn_remap_labels(const unsigned char* labels, long long n, const long long* lut, int lut_size,
                        int offset, long long invalid, long long* out, void* stream);
 
+/* GPU train / val augmentation (CitySegmentation._sync_transform / _val_sync_transform,
+ * data_loader/cityscapes.py:93-150; the same code in tusimple.py): mirror, short-edge rescale
+ * (PIL bilinear for the image, nearest for the mask), zero pad, crop, optional Gaussian blur,
+ * ToTensor + Normalize and the label remap, one launch per batch, the same pixels as PIL.
+ *
+ * fscnn_sync_tables (host only, no GPU): PIL's resize tables of ONE axis of ONE sample for the
+ *   `count` output positions start .. start+count-1 of a resize in_size -> out_size:
+ *   bounds[count][2] = (first source index, taps), coef[count][kmax] = 22-bit fixed-point
+ *   triangle-filter weights, nearest[count] = the mask's source index.  Positions >= out_size
+ *   (the zero pad) get no taps and nearest -1.  *ksize = taps per position the resize needs
+ *   (kmax must be >= it); with all three tables null the call only reports *ksize.
+ *   in_size / out_size > 8 is E_INVALID.
+ * fscnn_sync_blur_weights (host only): the two 24-bit weights of PIL's GaussianBlur(radius)
+ *   box passes; radius must be in [0, 1) (all the reference draws), else E_INVALID.
+ * fscnn_sync_transform: `blob` is N descriptors followed by their tables (int32; descriptor
+ *   offsets count int32s from the blob's start), once in host memory (validated here: every
+ *   table index is range-checked before the launch) and once, the same bytes, in device memory
+ *   (what the kernel reads; the caller orders the copy before this call on `stream`).  Writes
+ *   x [N,3,crop,crop] (out_dtype 0 fp32 / 1 bf16; (v/255 - mean[c])/std[c] as
+ *   fscnn_normalize_u8), target [N,crop,crop] int64 = lut[id + lut_offset] (ids outside the
+ *   table -> -1; pad -> id 0) and, unless null, crop_u8 [N,crop,crop,3].  lut is a device
+ *   array, mean / std are host arrays of 3 floats. */
+typedef struct fscnn_sync_desc {
+  const unsigned char* image; /* device uint8 [H][W][3] */
+  const unsigned char* mask;  /* device uint8 [H][W] */
+  int H, W;
+  int flip;                   /* read column W-1-x */
+  int ow, oh, x1, y1;         /* resized size (before the pad) and the crop's origin */
+  int blur;                   /* 0 / 1 */
+  unsigned ww, fw;            /* fscnn_sync_blur_weights */
+  int kx, ky;                 /* row stride of the coefficient tables */
+  int off_xb, off_xk, off_yb, off_yk, off_nx, off_ny; /* bounds / coef / nearest, x and y axis */
+} fscnn_sync_desc;
+int fscnn_sync_tables(int in_size, int out_size, int start, int count, int kmax, int* bounds,
+                      int* coef, int* nearest, int* ksize);
+int fscnn_sync_blur_weights(float radius, unsigned* ww, unsigned* fw);
+int fscnn_sync_transform(const void* host_blob, const void* device_blob, long long blob_bytes,
+                         int N, int crop, const long long* lut, int lut_size, int lut_offset,
+                         const float* mean, const float* std, void* x, int out_dtype,
+                         long long* target, unsigned char* crop_u8, void* stream);
+
 /* Fused training step head (train plans only): forward + bilinear upsample + CE(ignore_index)
  * evaluated at low resolution; loss2[0] = mean loss, loss2[1] = valid pixel count.  Computes
  * exactly criterion(model(x)[0], target) of train.py:270-271 without materialising the
