@@ -559,6 +559,58 @@ int fscnn_backward_loss(const fscnn_plan* plan, const float* grad_loss, const fl
   GUARD(net_backward(plan->plan, r, stage_from, stage_to));
 }
 
+long long fscnn_dice_head_ws_bytes(const fscnn_plan* plan) {
+  if (!plan || plan->plan.train != 1) {
+    set_error("fscnn_dice_head_ws_bytes: the fused loss head needs a training plan (train=1)");
+    return E_INVALID;
+  }
+  const Plan& pl = plan->plan;
+  return dice_head_ws_bytes(pl.N, pl.H3, pl.W3, pl.net->num_classes, pl.Cp);
+}
+
+int fscnn_forward_loss_dice(const fscnn_plan* plan, const void* x, int x_dtype,
+                            const long long* target, float smooth, float dice_weight,
+                            float focal_weight, float alpha, float gamma, float* loss_out,
+                            double* stats, const float* params, float* running, long long* nbt,
+                            void* ws, void* head_ws, unsigned long long seed, float dropout_p,
+                            float momentum, void* stream) {
+  if (!plan || !x || !target || !loss_out || !stats || !params || !running || !ws || !head_ws) {
+    set_error("fscnn_forward_loss_dice: null argument");
+    return E_INVALID;
+  }
+  RunArgs r{};
+  r.x = x; r.x_dtype = x_dtype; r.out = nullptr; r.out_dtype = plan->plan.dtype;
+  r.P = params; r.R = running; r.NBT = nbt; r.ws = ws;
+  r.seed = seed; r.dropout_p = dropout_p; r.momentum = momentum; r.st = S(stream);
+  r.target = target; r.ignore_index = -1; r.loss2 = loss_out;
+  r.head = HEAD_DICE; r.smooth = smooth; r.dice_weight = dice_weight;
+  r.focal_weight = focal_weight; r.alpha = alpha; r.gamma = gamma;
+  r.head_ws = head_ws; r.dice_stats = stats;
+  GUARD(net_forward(plan->plan, r));
+}
+
+int fscnn_backward_loss_dice(const fscnn_plan* plan, const float* grad_loss, const double* stats,
+                             float smooth, float dice_weight, float focal_weight, const void* x,
+                             int x_dtype, const float* params, float* grads, void* ws, void* bws,
+                             void* head_ws, unsigned long long seed, float dropout_p,
+                             int stage_from, int stage_to, void* stream) {
+  if (!plan || !grad_loss || !stats || !x || !params || !grads || !ws || !bws || !head_ws) {
+    set_error("fscnn_backward_loss_dice: null argument");
+    return E_INVALID;
+  }
+  if (plan->plan.net->aux) {
+    set_error("backward_loss: the fused loss head covers the main output only (aux net)");
+    return E_UNSUPPORTED;
+  }
+  RunArgs r{};
+  r.gloss = grad_loss;
+  r.head = HEAD_DICE; r.smooth = smooth; r.dice_weight = dice_weight;
+  r.focal_weight = focal_weight; r.head_ws = head_ws; r.dice_stats = const_cast<double*>(stats);
+  r.x = x; r.x_dtype = x_dtype; r.P = params; r.G = grads; r.ws = ws; r.bws = bws;
+  r.seed = seed; r.dropout_p = dropout_p; r.st = S(stream);
+  GUARD(net_backward(plan->plan, r, stage_from, stage_to));
+}
+
 int fscnn_backward_dx(const fscnn_plan* plan, const void* dout, const void* daux,
                       const float* grad_loss, const float* loss2, const void* x, int x_dtype,
                       void* dx, int dx_dtype, const float* params, float* grads, void* ws,

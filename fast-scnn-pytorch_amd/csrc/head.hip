@@ -762,4 +762,405 @@ int ce_head_scale(const float* g_raw, void* g, long long M, int C, int ld, const
   return check_launch("ce_head_scale");
 }
 
+// ---- Dice / Focal+Dice head (utils/loss.py:12-100) -------------------------------------------
+// The same work layout as ce_head_kernel (workgroup = (low-res row, image), thread = low-res
+// column, two logit rows in LDS, every full-resolution pixel once, neighbour shares added in a
+// fixed order).  Per pixel p = softmax(z), p1 = p[1], t = float(target) (targets outside [0, C)
+// count as 0):
+//   sums      I = sum p1 t, S = sum p1, T = sum t, F = sum alpha (1 - pt)^gamma ce
+//   loss      wd (1 - (2 I + s) / U) + wf F / npix,  U = S + T + s
+//   gradient  dz_c = (a t + b) p1 ([c == 1] - p_c) + f dfocal/dce (p_c - [c == t]),
+//             a = -2 wd / U, b = wd (2 I + s) / U^2, f = wf / npix.
+// a and b need the global sums, but dz is linear in (a, b, f):
+//   MODE 0 (C == 2, one pass): with two classes dz_0 = -dz_1, so the pass accumulates the three
+//     coefficient planes of channel 1 only, interleaved per low-res cell as (Ga, Gb, Gf) =
+//     sum w (t q, q, dfocal/dce (p1 - [t == 1])), q = p1 p0; dice_head_scale combines them with
+//     (a, b, f) from the device-resident sums.
+//   MODE 1 / MODE 2 (3 <= C <= HD_CMAX, two passes): three planes x C classes x 4 taps do not fit
+//     the register file, so pass 1 forms only the sums and pass 2, after the finalize, reads
+//     (a, b) from the device sums and accumulates the one combined plane a Ga + b Gb + f Gf.
+// Probabilities are evaluated per pixel (v_exp_f32 / v_rcp_f32 / v_log_f32, 1 ulp) for every plan
+// dtype; 1 - pt is the sum of the other classes' probabilities (no cancellation at pt -> 1).
+__device__ __forceinline__ float hd_pow(float x, float g) {  // x in [0, 1]
+  if (x > 0.f) return __builtin_amdgcn_exp2f(g * __builtin_amdgcn_logf(x));
+  return g == 0.f ? 1.f : 0.f;
+}
+
+struct DiceCoef {
+  float a, b, f;
+};
+__device__ __forceinline__ DiceCoef dice_coef(const double* stats, float smooth, float wd, float wf,
+                                              double npix) {
+  const double U = stats[1] + stats[2] + (double)smooth;
+  DiceCoef k;
+  k.a = (float)(-2.0 * wd / U);
+  k.b = (float)(wd * (2.0 * stats[0] + smooth) / (U * U));
+  k.f = (float)((double)wf / npix);
+  return k;
+}
+
+template <typename T, int CT, bool EXACT, int MODE>
+__global__ __launch_bounds__(HD_T) void dice_head_kernel(DiceHeadArgs a) {
+  constexpr int SL = (CT % 2 == 0) ? CT + 1 : CT;  // odd LDS stride per column
+  constexpr int NA = MODE == 0 ? 3 : (MODE == 1 ? 1 : CT);  // accumulated scalars per tap
+  static_assert(MODE != 0 || CT == 2, "the one-pass form is the two-class form");
+  static_assert(NA <= SL, "the neighbour hand-off reuses the logit rows' LDS");
+  __shared__ float s_L[2 * (HD_T + 1) * SL];
+  __shared__ float s_carry[2 * NA];
+  __shared__ __attribute__((aligned(8))) signed char s_t[2 * HD_TMAX];
+  __shared__ float s_r[4][HD_T];
+  const int tid = threadIdx.x;
+  const int hl = blockIdx.x, n = blockIdx.y;
+  const int Hl = a.Hl, Wl = a.Wl, H = a.H, W = a.W, ldl = a.ldl, gld = a.gld;
+  const int Cm = EXACT ? CT : a.C;
+  const float sh = ac_scale(Hl, H), sw = ac_scale(Wl, W);
+  const int h_lo = hd_first_ge(hl, Hl, H, sh), h_hi = hd_first_ge(hl + 1, Hl, H, sh);
+  const int hl1 = min(hl + 1, Hl - 1);
+  const T* lg = (const T*)a.logits + (size_t)n * Hl * Wl * ldl;
+  float* g0 = a.planes;                                // own-row plane
+  float* g1 = a.planes + (size_t)a.N * Hl * Wl * gld;  // spill plane (row hl+1)
+  const long long* tgt = a.target + (size_t)n * H * W;
+  const bool focal = a.focal != 0;
+  DiceCoef kf{0.f, 0.f, 0.f};
+  if (MODE == 2) kf = dice_coef(a.stats, a.smooth, a.wd, a.wf, (double)a.N * H * W);
+  float sI = 0.f, sS = 0.f, sT = 0.f, sF = 0.f;
+  if (tid < 2 * NA) s_carry[tid] = 0.f;
+  if (MODE != 1 && hl == 0) {  // nothing spills into row 0
+    for (int i = tid; i < Wl * gld; i += HD_T) g1[(size_t)n * Hl * Wl * gld + i] = 0.f;
+  }
+  // targets: one full-resolution row at a time in LDS as int8 (the next row's loads in flight
+  // during the current row), from the plan's packed int8 copy (8 per thread) or the int64 rows;
+  // rows wider than HD_TMAX are read per pixel
+  const bool lds_t = W <= HD_TMAX;
+  const bool t8 = a.tgt8 != nullptr && lds_t && W % 8 == 0;
+  const bool t8own = tid * 8 < W;
+  const signed char* trow8 = a.tgt8 + (size_t)n * H * W + tid * 8;
+  constexpr int TPT = HD_TMAX / HD_T;
+  for (int cb = 0; cb < Wl; cb += HD_T) {
+    __syncthreads();
+    for (int i = tid; i < 2 * (HD_T + 1) * CT; i += HD_T) {
+      const int c = i % CT, jr = i / CT;
+      const int j = jr % (HD_T + 1), r = jr / (HD_T + 1);
+      const int col = min(cb + j, Wl - 1);
+      const int row = r ? hl1 : hl;
+      // staged in log2 units: the softmax runs on v_exp_f32 (2^x)
+      s_L[(r * (HD_T + 1) + j) * SL + c] =
+          c < Cm ? ld1(lg + ((size_t)row * Wl + col) * ldl + c) * HD_LOG2E : 0.f;
+    }
+    __syncthreads();
+    const int t = cb + tid;
+    const bool active = t < Wl;
+    f32x2 a0[NA], a1[NA];  // (acc00, acc01) own row, columns t / t+1; (acc10, acc11) row hl+1
+#pragma unroll
+    for (int c = 0; c < NA; ++c) a0[c] = a1[c] = f32x2{0.f, 0.f};
+    const int w_lo = active ? hd_first_ge(t, Wl, W, sw) : 0;
+    const int w_hi = active ? hd_first_ge(t + 1, Wl, W, sw) : 0;
+    int tnext[TPT];
+    uint2 tq = make_uint2(0u, 0u);
+    auto load_trow = [&](int h) {
+      if (t8) {
+        if (t8own) tq = *reinterpret_cast<const uint2*>(trow8 + (size_t)h * W);
+        return;
+      }
+      const long long* tr = tgt + (size_t)h * W;
+#pragma unroll
+      for (int k = 0; k < TPT; ++k) {
+        const int w = tid + HD_T * k;
+        const long long tg = tr[w < W ? w : 0];
+        tnext[k] = (w < W && tg >= 0 && tg < Cm) ? (int)tg : 0;
+      }
+    };
+    if (lds_t && h_lo < h_hi) load_trow(h_lo);
+    const float* L0 = &s_L[tid * SL];
+    const float* L1 = &s_L[((HD_T + 1) + tid) * SL];
+    for (int h = h_lo; h < h_hi; ++h) {
+      signed char* trow_s = s_t + (h & 1) * HD_TMAX;
+      if (lds_t) {
+        if (t8) {
+          if (t8own) *reinterpret_cast<uint2*>(trow_s + tid * 8) = tq;
+        } else {
+#pragma unroll
+          for (int k = 0; k < TPT; ++k)
+            if (tid + HD_T * k < W) trow_s[tid + HD_T * k] = (signed char)tnext[k];
+        }
+        __syncthreads();
+        if (h + 1 < h_hi) load_trow(h + 1);
+      }
+      if (active) {
+        const Lerp lh = ac_lerp(h, Hl, H, sh);
+        float v0[CT], dv[CT];  // row-interpolated logits of column t, and (column t+1) - v0
+#pragma unroll
+        for (int c = 0; c < CT; ++c) {
+          v0[c] = fmaf(lh.l1, L1[c], lh.l0 * L0[c]);
+          dv[c] = fmaf(lh.l1, L1[SL + c], lh.l0 * L0[SL + c]) - v0[c];
+        }
+        const long long* trow = tgt + (size_t)h * W;
+        for (int w = w_lo; w < w_hi; ++w) {
+          const Lerp lw = ac_lerp(w, Wl, W, sw);
+          int ti;
+          if (lds_t) {
+            ti = trow_s[w];
+            ti = ti < 0 ? 0 : ti;  // packed: -1 = outside [0, C)
+          } else {
+            const long long tg = trow[w];
+            ti = (tg >= 0 && tg < Cm) ? (int)tg : 0;
+          }
+          const float tf = (float)ti;
+          float e[CT];
+          float mx = -INFINITY;
+#pragma unroll
+          for (int c = 0; c < CT; ++c) {
+            e[c] = fmaf(lw.l1, dv[c], v0[c]);
+            if (c < Cm) mx = fmaxf(mx, e[c]);
+          }
+          float se = 0.f, lt = 0.f, et = 0.f, so = 0.f;  // so: sum of the non-target exponentials
+#pragma unroll
+          for (int c = 0; c < CT; ++c) {
+            const float x = c < Cm ? __builtin_amdgcn_exp2f(e[c] - mx) : 0.f;
+            if (c == ti) lt = e[c], et = x;
+            else so += x;
+            se += x;
+            e[c] = x;
+          }
+          const float inv = __builtin_amdgcn_rcpf(se);
+          const float p1 = e[1] * inv;
+          float dfdce = 0.f;
+          if (focal) {
+            const float ce = (mx - lt + __builtin_amdgcn_logf(se)) * HD_LN2;
+            const float pt = et * inv, om = so * inv;
+            const float pg = hd_pow(om, a.gamma);
+            if (MODE != 2) sF = fmaf(a.alpha * pg, ce, sF);
+            if (MODE != 1) dfdce = a.alpha * (pg + ce * a.gamma * hd_pow(om, a.gamma - 1.f) * pt);
+          }
+          if (MODE != 2) {
+            sI = fmaf(p1, tf, sI);
+            sS += p1;
+            sT += tf;
+          }
+          if (MODE != 1) {
+            const f32x2 k0 = {lh.l0 * lw.l0, lh.l0 * lw.l1};
+            const f32x2 k1 = {lh.l1 * lw.l0, lh.l1 * lw.l1};
+            if (MODE == 0) {
+              const float q = p1 * (e[0] * inv);
+              const float gv[3] = {tf * q, q, dfdce * (p1 - (ti == 1 ? 1.f : 0.f))};
+#pragma unroll
+              for (int j = 0; j < 3; ++j) {
+                const f32x2 gg = {gv[j], gv[j]};
+                a0[j] = __builtin_elementwise_fma(k0, gg, a0[j]);
+                a1[j] = __builtin_elementwise_fma(k1, gg, a1[j]);
+              }
+            } else {
+              const float cp = fmaf(kf.a, tf, kf.b) * p1, cf = kf.f * dfdce;
+#pragma unroll
+              for (int c = 0; c < NA; ++c) {
+                const float pc = e[c] * inv;
+                const float gc = cp * ((c == 1 ? 1.f : 0.f) - pc) + cf * (pc - (c == ti ? 1.f : 0.f));
+                const f32x2 gg = {gc, gc};
+                a0[c] = __builtin_elementwise_fma(k0, gg, a0[c]);
+                a1[c] = __builtin_elementwise_fma(k1, gg, a1[c]);
+              }
+            }
+          }
+        }
+      }
+    }
+    if (MODE == 1) continue;  // the sums pass writes no plane (uniform: no barrier is skipped)
+    float acc00[NA], acc01[NA], acc10[NA], acc11[NA];
+#pragma unroll
+    for (int c = 0; c < NA; ++c) {
+      acc00[c] = a0[c].x;
+      acc01[c] = a0[c].y;
+      acc10[c] = a1[c].x;
+      acc11[c] = a1[c].y;
+    }
+    if (active) {
+      if (t == Wl - 1) {  // i1(w) == i0(w) on the last column: both taps are column t
+#pragma unroll
+        for (int c = 0; c < NA; ++c) {
+          acc00[c] += acc01[c];
+          acc10[c] += acc11[c];
+          acc01[c] = acc11[c] = 0.f;
+        }
+      }
+      if (hl1 == hl) {  // last row: both row taps are row hl
+#pragma unroll
+        for (int c = 0; c < NA; ++c) {
+          acc00[c] += acc10[c];
+          acc01[c] += acc11[c];
+          acc10[c] = acc11[c] = 0.f;
+        }
+      }
+    }
+    // ---- hand the (*, t+1) shares to thread t+1 through LDS -------------------------------
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < NA; ++c) {
+      s_L[tid * SL + c] = acc01[c];
+      s_L[((HD_T + 1) + tid) * SL + c] = acc11[c];
+    }
+    __syncthreads();
+    if (active) {
+      float* o0 = g0 + (((size_t)n * Hl + hl) * Wl + t) * gld;
+      float* o1 = g1 + (((size_t)n * Hl + hl + 1) * Wl + t) * gld;
+      const int nw = MODE == 0 ? 3 : Cm;
+#pragma unroll
+      for (int c = 0; c < NA; ++c) {
+        if (c < nw) {
+          const float left0 = tid > 0 ? s_L[(tid - 1) * SL + c] : s_carry[c];
+          const float left1 = tid > 0 ? s_L[((HD_T + 1) + tid - 1) * SL + c] : s_carry[NA + c];
+          o0[c] = acc00[c] + left0;
+          if (hl1 != hl) o1[c] = acc10[c] + left1;
+        }
+      }
+    }
+    __syncthreads();
+    if (tid == HD_T - 1) {  // column cb + HD_T starts the next chunk
+#pragma unroll
+      for (int c = 0; c < NA; ++c) {
+        s_carry[c] = acc01[c];
+        s_carry[NA + c] = acc11[c];
+      }
+    }
+  }
+  if (MODE == 2) return;
+  s_r[0][tid] = sI;
+  s_r[1][tid] = sS;
+  s_r[2][tid] = sT;
+  s_r[3][tid] = sF;
+  __syncthreads();
+  for (int off = HD_T / 2; off > 0; off >>= 1) {
+    if (tid < off) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) s_r[k][tid] += s_r[k][tid + off];
+    }
+    __syncthreads();
+  }
+  if (tid < 4) a.part[4 * ((size_t)n * Hl + hl) + tid] = s_r[tid][0];
+}
+
+// partials [P][4] -> stats (I, S, T, F) in fp64, fixed order, and the loss
+__global__ __launch_bounds__(256) void dice_head_finalize_kernel(const float* part, int P,
+                                                                 float smooth, float wd, float wf,
+                                                                 double npix, double* stats,
+                                                                 float* loss) {
+  __shared__ double r[4][256];
+  double s[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int p = threadIdx.x; p < P; p += 256)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s[k] += part[4 * (size_t)p + k];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) r[k][threadIdx.x] = s[k];
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (threadIdx.x < off)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) r[k][threadIdx.x] += r[k][threadIdx.x + off];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const double I = r[0][0], S = r[1][0], Tt = r[2][0], F = r[3][0];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) stats[k] = r[k][0];
+    const double dice = (2.0 * I + smooth) / (S + Tt + smooth);
+    loss[0] = (float)((double)wd * (1.0 - dice) + (double)wf * F / npix);
+  }
+}
+
+long long dice_head_ws_bytes(int N, int Hl, int Wl, int C, int ldl) {
+  const long long M = (long long)N * Hl * Wl;
+  const long long planes = 2 * M * (C == 2 ? 3 : ldl) * 4;
+  const long long part = (long long)N * Hl * 4 * 4;
+  return (planes + 255) / 256 * 256 + part;
+}
+
+template <typename T, int CT, bool EXACT, int MODE>
+static void dice_head_launch(const DiceHeadArgs& a, dim3 grid, hipStream_t st) {
+  prof_launch((dice_head_kernel<T, CT, EXACT, MODE>), grid, HD_T, 0, st, a);
+}
+template <int CT, bool EXACT, int MODE>
+static void dice_head_launch_dt(const DiceHeadArgs& a, int dtype, dim3 grid, hipStream_t st) {
+  if (dtype == DT_F32) dice_head_launch<float, CT, EXACT, MODE>(a, grid, st);
+  else if (dtype == DT_F16) dice_head_launch<f16, CT, EXACT, MODE>(a, grid, st);
+  else dice_head_launch<bf16, CT, EXACT, MODE>(a, grid, st);
+}
+template <int MODE>
+static void dice_head_launch_c(const DiceHeadArgs& a, int dtype, dim3 grid, hipStream_t st) {
+  if (a.C == 19) dice_head_launch_dt<19, true, MODE>(a, dtype, grid, st);
+  else if (a.C <= 8) dice_head_launch_dt<8, false, MODE>(a, dtype, grid, st);
+  else dice_head_launch_dt<HD_CMAX, false, MODE>(a, dtype, grid, st);
+}
+
+int dice_head(const DiceHeadArgs& a0, void* head_ws, float* loss, double* stats, int dtype,
+              hipStream_t st) {
+  if (a0.C < 2 || a0.C > HD_CMAX) {
+    set_error("dice_head: %d classes (2 .. %d)", a0.C, HD_CMAX);
+    return E_UNSUPPORTED;
+  }
+  DiceHeadArgs a = a0;
+  const long long M = (long long)a.N * a.Hl * a.Wl;
+  a.gld = a.C == 2 ? 3 : a.ldl;
+  a.planes = (float*)head_ws;
+  a.part = (float*)((char*)head_ws + ((2 * M * a.gld * 4 + 255) / 256 * 256));
+  a.stats = stats;
+  const dim3 grid(a.Hl, a.N);
+  const int P = a.N * a.Hl;
+  const double npix = (double)a.N * a.H * a.W;
+  const double lb = (dtype == DT_F32 ? 4.0 : 2.0) * M * a.C, tb = (a.tgt8 ? 1.0 : 8.0) * npix;
+  if (a.C == 2) {
+    ProfScope ps(PK_CE, st, lb + tb + 2.0 * 4.0 * M * 3, 0.0);
+    dice_head_launch_dt<2, true, 0>(a, dtype, grid, st);
+    if (int rc = check_launch("dice_head")) return rc;
+    prof_launch(dice_head_finalize_kernel, 1, 256, 0, st, a.part, P, a.smooth, a.wd, a.wf, npix,
+                stats, loss);
+    return check_launch("dice_head_finalize");
+  }
+  ProfScope ps(PK_CE, st, 2.0 * (lb + tb) + 2.0 * 4.0 * M * a.C, 0.0);
+  dice_head_launch_c<1>(a, dtype, grid, st);
+  if (int rc = check_launch("dice_head (sums)")) return rc;
+  prof_launch(dice_head_finalize_kernel, 1, 256, 0, st, a.part, P, a.smooth, a.wd, a.wf, npix,
+              stats, loss);
+  if (int rc = check_launch("dice_head_finalize")) return rc;
+  dice_head_launch_c<2>(a, dtype, grid, st);
+  return check_launch("dice_head (gradient)");
+}
+
+// g[m][c] = gout * (a Ga + b Gb + f Gf) (two classes: channel 1, channel 0 its negative) or
+// gout * the combined plane (general C); own-row plane + the spill of the row above, fixed order
+template <typename T>
+__global__ __launch_bounds__(256) void dice_head_scale_kernel(const float* planes, T* g, int M,
+                                                              int C, int ld, const float* gout,
+                                                              const double* stats, float smooth,
+                                                              float wd, float wf, double npix) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= M * ld) return;
+  const int c = i % ld, m = i / ld;
+  float v = 0.f;
+  if (C == 2) {
+    if (c < 2) {
+      const DiceCoef k = dice_coef(stats, smooth, wd, wf, npix);
+      const float* o = planes + (size_t)m * 3;
+      const float* s = planes + ((size_t)M + m) * 3;
+      v = k.a * (o[0] + s[0]) + k.b * (o[1] + s[1]) + k.f * (o[2] + s[2]);
+      v = (c == 1 ? v : -v) * gout[0];
+    }
+  } else if (c < C) {
+    v = (planes[i] + planes[(size_t)M * ld + i]) * gout[0];
+  }
+  st1(g + i, v);
+}
+
+int dice_head_scale(const void* head_ws, void* g, long long M, int C, int ld, const float* gout,
+                    const double* stats, float smooth, float wd, float wf, double npix, int dtype,
+                    hipStream_t st) {
+  const int total = (int)(M * ld);
+  const float* pl = (const float*)head_ws;
+  if (dtype == DT_F32)
+    prof_launch(dice_head_scale_kernel<float>, cdiv(total, 256), 256, 0, st, pl, (float*)g, (int)M, C, ld, gout, stats, smooth, wd, wf, npix);
+  else if (dtype == DT_F16)
+    prof_launch(dice_head_scale_kernel<f16>, cdiv(total, 256), 256, 0, st, pl, (f16*)g, (int)M, C, ld, gout, stats, smooth, wd, wf, npix);
+  else
+    prof_launch(dice_head_scale_kernel<bf16>, cdiv(total, 256), 256, 0, st, pl, (bf16*)g, (int)M, C, ld, gout, stats, smooth, wd, wf, npix);
+  return check_launch("dice_head_scale");
+}
+
 }  // namespace fscnn

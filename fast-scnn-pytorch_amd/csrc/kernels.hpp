@@ -351,6 +351,24 @@ struct CeHeadArgs {
   const signed char* tgt8 = nullptr;
 };
 
+// Fused Dice / Focal+Dice training head (head.hip): the same upsample + loss + low-res gradient
+// as CeHeadArgs for utils/loss.py:12-100.  dice_head fills planes / gld / part / stats itself
+// from the caller's head_ws (dice_head_ws_bytes) and stats buffers.
+struct DiceHeadArgs {
+  int N, C, Hl, Wl, H, W;
+  const void* logits;        // NHWC [N][Hl][Wl][ldl]
+  int ldl;
+  const long long* target;   // [N][H][W]; values outside [0, C) count as t = 0
+  const signed char* tgt8 = nullptr;  // optional packed targets (ce_pack_targets, ignore = -1)
+  float alpha = 0.5f, gamma = 2.f;
+  int focal = 0;             // compute the focal term (focal_weight != 0)
+  float smooth = 1e-6f, wd = 1.f, wf = 0.f;
+  float* planes = nullptr;   // 2 planes [N][Hl][Wl][gld] fp32: own row, spill from the row above
+  int gld = 0;               // 3 (two classes: Ga, Gb, Gf of channel 1) or ldl (combined plane)
+  float* part = nullptr;     // [N * Hl][4]
+  const double* stats = nullptr;  // (I, S, T, F), written by the finalize
+};
+
 struct DropArgs {
   int N, H, W, C;
   const void* x; int ldx;
@@ -629,6 +647,15 @@ int ce_pack_targets(const long long* t, long long n, int C, long long ignore_ind
 // g[m][c] = g_raw[m][c] * gout / count  (c < C; pad columns zeroed)
 int ce_head_scale(const float* g_raw, void* g, long long M, int C, int ld, const float* gout,
                   const float* out2, int dtype, hipStream_t st);
+// Dice / Focal+Dice head: loss[0] and stats[4] (I, S, T, F; fp64) are device outputs; head_ws
+// (dice_head_ws_bytes, 256-B aligned) keeps the coefficient planes for dice_head_scale, which
+// writes g = gout * (a Ga + b Gb + f Gf) (pad columns zeroed) in the plan dtype
+long long dice_head_ws_bytes(int N, int Hl, int Wl, int C, int ldl);
+int dice_head(const DiceHeadArgs& a, void* head_ws, float* loss, double* stats, int dtype,
+              hipStream_t st);
+int dice_head_scale(const void* head_ws, void* g, long long M, int C, int ld, const float* gout,
+                    const double* stats, float smooth, float wd, float wf, double npix, int dtype,
+                    hipStream_t st);
 int dropout(const DropArgs& a, int dtype, hipStream_t st);
 // GPU input path: ToTensor + Normalize of uint8 HWC images into NCHW (fp32 / bf16)
 int normalize_u8(const uint8_t* x, int N, int H, int W, const float* mean, const float* std,

@@ -1352,6 +1352,16 @@ struct Exec {
         set_error("forward_loss needs a training plan (train=1)");
         return E_INVALID;
       }
+      if (r.head == HEAD_DICE) {
+        g_prof_tag = "head (upsample + dice)";
+        DiceHeadArgs h{};
+        h.N = N; h.C = net.num_classes; h.Hl = pl.H3; h.Wl = pl.W3; h.H = pl.H; h.W = pl.W;
+        h.logits = W(pl.logits); h.ldl = pl.Cp; h.target = r.target;
+        if (pack) h.tgt8 = (const signed char*)W(pl.tgt8);
+        h.alpha = r.alpha; h.gamma = r.gamma; h.focal = r.focal_weight != 0.f;
+        h.smooth = r.smooth; h.wd = r.dice_weight; h.wf = r.focal_weight;
+        return dice_head(h, r.head_ws, r.loss2, r.dice_stats, dt, r.st);
+      }
       g_prof_tag = "head (upsample + cross entropy)";
       CeHeadArgs h{};
       h.N = N; h.C = net.num_classes; h.Hl = pl.H3; h.Wl = pl.W3; h.H = pl.H; h.W = pl.W;
@@ -1759,7 +1769,12 @@ struct Exec {
   int backward_head() {
     g_prof_tag = "head (backward) + classifier.conv";
     const int N = pl.N, C = net.num_classes;
-    if (r.gloss) {
+    if (r.gloss && r.head == HEAD_DICE) {
+      // fused Dice head: combine the forward's coefficient planes with the device-resident sums
+      TRY(dice_head_scale(r.head_ws, Bw(pl.g_logits), pl.c2pw.M, C, pl.Cp, r.gloss, r.dice_stats,
+                          r.smooth, r.dice_weight, r.focal_weight, (double)N * pl.H * pl.W, dt,
+                          r.st));
+    } else if (r.gloss) {
       // fused head: the low-res logits gradient was gathered in the forward; scale by dL/dloss / count
       TRY(ce_head_scale(Wf(pl.g_raw), Bw(pl.g_logits), pl.c2pw.M, C, pl.Cp, r.gloss, r.loss2, dt,
                         r.st));
@@ -2069,7 +2084,9 @@ std::vector<uint64_t> run_key(int kind, int s0, int s1, const RunArgs& r) {
   return {(uint64_t)kind, (uint64_t)s0, (uint64_t)s1, P(r.x), (uint64_t)r.x_dtype, P(r.out),
           (uint64_t)r.out_dtype, P(r.aux_out), P(r.labels), (uint64_t)r.label_u8, P(r.P), P(r.R), P(r.NBT), P(r.G), P(r.ws),
           P(r.bws), P(r.dout), P(r.daux), fbits(r.dropout_p), fbits(r.momentum), P(r.target),
-          (uint64_t)r.ignore_index, P(r.loss2), P(r.gloss), P(r.dx), (uint64_t)r.dx_dtype};
+          (uint64_t)r.ignore_index, P(r.loss2), P(r.gloss), P(r.dx), (uint64_t)r.dx_dtype,
+          (uint64_t)r.head, fbits(r.smooth), fbits(r.dice_weight), fbits(r.focal_weight),
+          fbits(r.alpha), fbits(r.gamma), P(r.head_ws), P(r.dice_stats)};
 }
 
 template <typename F>

@@ -138,6 +138,8 @@ bool ir_block_shape(const Net& net, const Plan& pl, int i, IrArgs& b);
 std::shared_ptr<GraphCache> make_graph_cache();
 std::shared_ptr<SideStream> make_side_stream();
 
+enum { HEAD_CE = 0, HEAD_DICE = 1 };
+
 struct RunArgs {
   const void* x; int x_dtype;     // NCHW input image
   void* out; int out_dtype;       // NCHW logits [N][C][H][W]
@@ -161,6 +163,14 @@ struct RunArgs {
   long long ignore_index = -1;
   float* loss2 = nullptr;
   const float* gloss = nullptr;
+  // head kind of the fused loss head: HEAD_CE (above) or HEAD_DICE, the Dice / Focal+Dice
+  // criteria (utils/loss.py:12-100).  Dice: forward writes the loss into loss2[0] and the sums
+  // (I, S, T, F) into dice_stats; the coefficient planes live in head_ws
+  // (dice_head_ws_bytes), which the backward reads again.
+  int head = 0;
+  float smooth = 1e-6f, dice_weight = 1.f, focal_weight = 0.f, alpha = 0.5f, gamma = 2.f;
+  void* head_ws = nullptr;
+  double* dice_stats = nullptr;
   // eval prediction: forward with labels != null writes argmax(upsampled logits) instead of out
   void* labels = nullptr;
   int label_u8 = 0;

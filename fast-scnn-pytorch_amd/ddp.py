@@ -146,6 +146,11 @@ class DistributedFastSCNN(torch.nn.Module):
     def forward(self, *args, **kwargs):
         return self.module(*args, **kwargs)
 
-    def forward_loss(self, x, target, ignore_index=-1):
-        """Fused forward + CE of the local shard; backward all-reduces gradients per stage."""
-        return self.module.forward_loss(x, target, ignore_index=ignore_index)
+    def forward_loss(self, x, target, ignore_index=-1, criterion=None):
+        """Fused forward + loss of the local shard; backward all-reduces gradients per stage.
+
+        ``criterion`` as in ``FastSCNN.forward_loss``.  The Dice criteria's sums (intersection,
+        prediction and target mass) are taken over this rank's shard, as they are per replica
+        under the reference's DistributedDataParallel: the averaged gradient is the mean of the
+        per-rank Dice gradients, not the gradient of one Dice over the global batch."""
+        return self.module.forward_loss(x, target, ignore_index=ignore_index, criterion=criterion)

@@ -284,12 +284,55 @@ class _FastSCNNFunction(torch.autograd.Function):
         return (dx, None, None) + tuple(grads)
 
 
+def _head_spec(criterion, ignore_index=-1):
+    """The fused loss head a criterion object maps to, as a tuple:
+
+    ``("ce", ignore_index)`` or ``("dice", smooth, dice_weight, focal_weight, alpha, gamma)``.
+
+    Duck-typed on the class name and the attributes of utils/loss.py, so this package's criteria
+    (``loss.py``) and the reference's own ``utils.loss`` objects (what train.py:183-191 builds)
+    resolve alike; ``None`` is the CE head with the given ``ignore_index``.  Criteria without a
+    fused head (the OHEM criterion, anything unknown) raise ``RuntimeError``."""
+    if criterion is None:
+        return ("ce", int(ignore_index))
+    names = [c.__name__ for c in type(criterion).__mro__]
+    if "SoftmaxCrossEntropyOHEMLoss" in names or "MixSoftmaxCrossEntropyOHEMLoss" in names:
+        raise RuntimeError("forward_loss: the OHEM criterion has no fused loss head; use the "
+                           "unfused path, criterion(model(x), target)")
+    if "FocalDiceLoss" in names:
+        inner = getattr(criterion, "dice_loss", None)  # the reference keeps smooth there
+        smooth = inner.smooth if inner is not None else criterion.smooth
+        dw = float(criterion.dice_weight)
+        return ("dice", float(smooth), dw, 1.0 - dw, float(criterion.alpha),
+                float(criterion.gamma))
+    if "MixDiceLoss" in names:
+        return ("dice", float(criterion.dice_loss.smooth), 1.0, 0.0, 0.5, 2.0)
+    if "DiceLoss" in names:
+        return ("dice", float(criterion.smooth), 1.0, 0.0, 0.5, 2.0)
+    if "MixSoftmaxCrossEntropyLoss" in names:
+        return ("ce", int(criterion.ignore_index))
+    raise RuntimeError("forward_loss: no fused loss head for %s; use the unfused path, "
+                       "criterion(model(x), target)" % type(criterion).__name__)
+
+
 class _FastSCNNLossFunction(torch.autograd.Function):
-    """Fused train step head: loss = CE(upsample(logits_lowres), target) at low resolution."""
+    """Fused train step head: loss = criterion(upsample(logits_lowres), target) at low
+    resolution.  ``head`` is the CE head's ignore_index (an int) or a Dice ``_head_spec`` tuple;
+    the Dice head's coefficient planes (``head_ws``) and sums (``stats``) travel to the backward
+    in ``ctx.dice``."""
 
     @staticmethod
-    def forward(ctx, x, target, ignore_index, model, ar, *params):
-        loss2, ws, seed, dt, xc = model._run_forward_loss(x, target, ignore_index, ar)
+    def forward(ctx, x, target, head, model, ar, *params):
+        ctx.dice = None
+        if isinstance(head, tuple):
+            if ctx.needs_input_grad[0]:
+                raise RuntimeError("forward_loss: the fused Dice head does not form the input "
+                                   "image's gradient; use criterion(model(x), target)")
+            loss2, ws, seed, dt, xc, head_ws, stats = model._run_forward_loss_dice(
+                x, target, head, ar)
+            ctx.dice = (head, head_ws, stats)
+        else:
+            loss2, ws, seed, dt, xc = model._run_forward_loss(x, target, head, ar)
         ctx.model, ctx.ar = model, ar
         ctx.ws, ctx.seed, ctx.dt, ctx.loss2 = ws, seed, dt, loss2
         ctx.x_dtype = x.dtype
@@ -306,8 +349,8 @@ class _FastSCNNLossFunction(torch.autograd.Function):
         g = gloss.to(torch.float32).reshape(1).contiguous()
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         grads = ctx.model._run_backward(None, x, ctx.ws, ctx.seed, ctx.dt, ctx.ar, gloss=g,
-                                        loss2=ctx.loss2, dx=dx)
-        ctx.ws = ctx.ar = None
+                                        loss2=ctx.loss2, dx=dx, dice=ctx.dice)
+        ctx.ws = ctx.ar = ctx.dice = None
         if dx is not None and dx.dtype != ctx.x_dtype:
             dx = dx.to(ctx.x_dtype)
         return (dx, None, None, None, None) + tuple(grads)
@@ -647,20 +690,88 @@ class FastSCNN(nn.Module):
             self._debug = {"plan": plan, "ws": ws, "dt": dt}
         return loss2, ws, seed, dt, x
 
-    def forward_loss(self, x, target, ignore_index=-1):
-        """Fused train-step head: ``criterion(self(x)[0], target)`` of train.py:270-271 for
-        ``nn.CrossEntropyLoss(ignore_index)`` (utils/loss.py:103-124), computed at the low-res
-        logit resolution without materialising full-resolution logits.  Same loss and gradients
-        as the unfused path (tests/test_gpu_model.py); requires train mode."""
+    def _run_forward_loss_dice(self, x, target, spec, ar):
+        """The forward of the fused Dice / Focal+Dice head (``spec``: a Dice ``_head_spec``)."""
+        if self.aux:
+            raise RuntimeError("forward_loss: the fused loss head covers the main output only; "
+                               "with aux=True use MixDiceLoss(aux=True)(model(x), target)")
+        if not x.is_cuda or not target.is_cuda:
+            raise RuntimeError("FastSCNN.forward_loss: the HIP path needs ROCm device tensors")
+        if not 2 <= self.num_classes <= 32:
+            raise RuntimeError("forward_loss: the fused Dice head takes 2 .. 32 classes; use "
+                               "criterion(model(x), target)")
+        nat = self.native()
+        N, _, H, W = x.shape
+        if tuple(target.shape) != (N, H, W):
+            raise RuntimeError("forward_loss: target %s does not match input %s"
+                               % (tuple(target.shape), tuple(x.shape)))
+        if N < 2:
+            raise ValueError("Expected more than 1 value per channel when training, got input "
+                             "size torch.Size([1, 32, 1, 1])")
+        dt = self._compute_dtype(x, True)
+        x = self._input(x)
+        target = target.to(torch.int64).contiguous()
+        from . import loss as _loss
+        if _loss.CHECK_TARGETS:
+            bad = (target < 0) | (target >= self.num_classes)  # no ignore_index in Dice
+            if bool(bad.any()):
+                raise IndexError("Target %d is out of bounds." % int(target[bad].flatten()[0]))
+        plan, fw, _ = nat.plan(N, H, W, _lib.dtype_code(dt), True, x.device)
+        ws = torch.empty(max(fw, 1), dtype=torch.uint8, device=x.device)
+        hb = int(_lib.load().fscnn_dice_head_ws_bytes(plan))
+        if hb < 0:
+            _lib.check(hb, "fscnn_dice_head_ws_bytes")
+        head_ws = torch.empty(max(hb, 1), dtype=torch.uint8, device=x.device)
+        stats = torch.empty(4, dtype=torch.float64, device=x.device)
+        loss1 = torch.empty(1, dtype=torch.float32, device=x.device)
+        _, smooth, dw, fw_, alpha, gamma = spec
+        p = self._dropout_p()
+        seed = 0
+        if p > 0:
+            fixed = getattr(self, "_dropout_seed", None)
+            seed = int(fixed) if fixed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
+        with torch.cuda.device(x.device):
+            _lib.call("fscnn_forward_loss_dice", plan, _lib.ptr(x), _lib.dtype_code(x.dtype),
+                      _lib.ptr(target), _lib.c_float(smooth), _lib.c_float(dw), _lib.c_float(fw_),
+                      _lib.c_float(alpha), _lib.c_float(gamma), _lib.ptr(loss1), _lib.ptr(stats),
+                      _lib.ptr(ar["P"]), _lib.ptr(ar["R"]), _lib.ptr(ar["NBT"]), _lib.ptr(ws),
+                      _lib.ptr(head_ws), _lib.c_ull(seed), _lib.c_float(p),
+                      _lib.c_float(self._momentum()), _lib.stream_ptr(x.device))
+        self._writeback(ar)
+        torch.autograd.graph.increment_version(ar["R"])
+        if getattr(self, "_keep_ws", False):
+            self._debug = {"plan": plan, "ws": ws, "dt": dt}
+        return loss1, ws, seed, dt, x, head_ws, stats
+
+    def forward_loss(self, x, target, ignore_index=-1, criterion=None):
+        """Fused train-step head: ``criterion(self(x)[0], target)`` of train.py:270-271, computed
+        at the low-res logit resolution without materialising full-resolution logits.  Same loss
+        and gradients as the unfused path (tests/test_gpu_model.py, tests/test_gpu_dice_head.py);
+        requires train mode.
+
+        ``criterion=None``: ``nn.CrossEntropyLoss(ignore_index)`` (utils/loss.py:103-124).
+        Otherwise the criterion object the training script built, this package's or the
+        reference's own (``_head_spec``): ``DiceLoss``, ``MixDiceLoss`` and ``FocalDiceLoss``
+        (utils/loss.py:12-100) take the fused Dice head, ``MixSoftmaxCrossEntropyLoss`` the CE
+        head with the criterion's ``ignore_index``; the OHEM criterion and anything else raise
+        ``RuntimeError`` (use ``criterion(model(x), target)``).
+
+        Dice targets outside ``[0, num_classes)`` are a caller error, as in the reference (its
+        focal term raises): with ``loss.CHECK_TARGETS`` they raise ``IndexError``, otherwise they
+        count as ``t = 0``.  The Dice head does not form the input image's gradient."""
         if not self.training:
             raise RuntimeError("forward_loss is the training step; call model.train() first")
         if not x.is_cuda:
             raise RuntimeError("FastSCNN.forward_loss: the HIP path needs ROCm device tensors")
+        head = ignore_index
+        if criterion is not None:
+            spec = _head_spec(criterion, ignore_index)
+            head = spec[1] if spec[0] == "ce" else spec
         ar = self._exec_arena(x.device)
-        return _FastSCNNLossFunction.apply(x, target, ignore_index, self, ar, *ar["params"])
+        return _FastSCNNLossFunction.apply(x, target, head, self, ar, *ar["params"])
 
     def _run_backward(self, gout, x, ws, seed, dt, ar, gloss=None, loss2=None, gaux=None,
-                      mode=MODE_TRAIN, dx=None):
+                      mode=MODE_TRAIN, dx=None, dice=None):
         """The staged native backward of a MODE_TRAIN / MODE_EVAL_GRAD forward whose workspace
         is ``ws``; parameter gradients are views of one flat arena G, and ``dx`` (dense NCHW,
         the dtype of ``x``) receives the input gradient when given."""
@@ -687,21 +798,28 @@ class FastSCNN(nn.Module):
             # its end, so the main stream does not wait for the side stream between stages
             with torch.cuda.device(x.device):
                 self._backward_stage(plan, (0, 3), gout, gaux, gloss, loss2, x, ar, G, ws, bws,
-                                     seed, p, dx)
+                                     seed, p, dx, dice)
         else:
             for s in range(4):
                 with torch.cuda.device(x.device):
                     self._backward_stage(plan, (s, s), gout, gaux, gloss, loss2, x, ar, G, ws,
-                                         bws, seed, p, dx)
+                                         bws, seed, p, dx, dice)
                 b, e = nat.stage_ranges[s]
                 hook(s, G, b, e)
         return [G[off:off + numel].view(prm.shape)
                 for prm, (_, off, numel) in zip(ar["params"], nat.params)]
 
     def _backward_stage(self, plan, stages, gout, gaux, gloss, loss2, x, ar, G, ws, bws, seed, p,
-                        dx=None):
+                        dx=None, dice=None):
         s0, s1 = stages  # backward stages s0 .. s1 (0: head ... 3: LearningToDownsample)
-        if dx is not None:  # the general entry point: also writes the input gradient (stage 3)
+        if dice is not None:  # the fused Dice head: (spec, head_ws, stats) of its forward
+            (_, smooth, dw, fw, _, _), head_ws, stats = dice
+            _lib.call("fscnn_backward_loss_dice", plan, _lib.ptr(gloss), _lib.ptr(stats),
+                      _lib.c_float(smooth), _lib.c_float(dw), _lib.c_float(fw), _lib.ptr(x),
+                      _lib.dtype_code(x.dtype), _lib.ptr(ar["P"]), _lib.ptr(G), _lib.ptr(ws),
+                      _lib.ptr(bws), _lib.ptr(head_ws), _lib.c_ull(seed), _lib.c_float(p), s0, s1,
+                      _lib.stream_ptr(x.device))
+        elif dx is not None:  # the general entry point: also writes the input gradient (stage 3)
             _lib.call("fscnn_backward_dx", plan, _lib.ptr(gout), _lib.ptr(gaux), _lib.ptr(gloss),
                       _lib.ptr(loss2), _lib.ptr(x), _lib.dtype_code(x.dtype), _lib.ptr(dx),
                       _lib.dtype_code(dx.dtype), _lib.ptr(ar["P"]), _lib.ptr(G), _lib.ptr(ws),

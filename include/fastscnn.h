@@ -237,6 +237,31 @@ int fscnn_backward_loss(const fscnn_plan* plan, const float* grad_loss, const fl
                         void* bws, unsigned long long dropout_seed, float dropout_p,
                         int stage_from, int stage_to, void* stream);
 
+/* The same fused step head for the Dice / Focal+Dice criteria (utils/loss.py:12-100, the default
+ * --loss-type of train.py:70): loss = dice_weight * (1 - (2 I + smooth) / (S + T + smooth)) +
+ * focal_weight * F / (N H W) with, over the full-resolution pixels of the upsampled logits,
+ * I = sum p1 t, S = sum p1, T = sum t, F = sum alpha (1 - pt)^gamma ce (p1 = softmax[:, 1],
+ * t = float(target); targets outside [0, num_classes) count as 0; F only when focal_weight != 0).
+ * DiceLoss / MixDiceLoss: dice_weight 1, focal_weight 0; FocalDiceLoss: dice_weight and
+ * 1 - dice_weight.  loss_out (float[1]) and stats (double[4] = I, S, T, F) are device outputs;
+ * nothing is read back by the host.  head_ws (fscnn_dice_head_ws_bytes, 256-B aligned) keeps
+ * the low-resolution coefficient planes until fscnn_backward_loss_dice, which takes d(loss)
+ * (device scalar) and the forward's stats and scalars.  num_classes 2 .. 32; an aux net
+ * returns -2.  fscnn_dice_head_ws_bytes is negative (fscnn_last_error set) unless the plan
+ * is a train = 1 plan; the plan's own workspace sizes do not include it. */
+long long fscnn_dice_head_ws_bytes(const fscnn_plan* plan);
+int fscnn_forward_loss_dice(const fscnn_plan* plan, const void* x, int x_dtype,
+                            const long long* target, float smooth, float dice_weight,
+                            float focal_weight, float alpha, float gamma, float* loss_out,
+                            double* stats, const float* params, float* running, long long* nbt,
+                            void* ws, void* head_ws, unsigned long long dropout_seed,
+                            float dropout_p, float momentum, void* stream);
+int fscnn_backward_loss_dice(const fscnn_plan* plan, const float* grad_loss, const double* stats,
+                             float smooth, float dice_weight, float focal_weight, const void* x,
+                             int x_dtype, const float* params, float* grads, void* ws, void* bws,
+                             void* head_ws, unsigned long long dropout_seed, float dropout_p,
+                             int stage_from, int stage_to, void* stream);
+
 /* ---- fused blocks (inference) ---------------------------------------------------------------
  * fscnn_block_ir_fwd: one stride-1 LinearBottleneck (models/fast_scnn.py:95-115) with its three
  * BatchNorms folded (eval): y = BN_p(W_p * relu(BN_d(dw3x3(relu(BN_e(W_e * x)))))) (+ x when
