@@ -9,7 +9,7 @@ Submodules:
   _lib           ctypes binding of the C-ABI library libfastscnn_hip.so (fails loudly if absent)
   fast_scnn      FastSCNN / get_fast_scnn — the reference interface, running on HIP kernels
   loss           fused cross-entropy criterion (HIP)
-  optim          fused multi-tensor SGD (HIP)
+  optim          fused multi-tensor SGD and AdamW (HIP)
   ddp            one-process-per-GPU data parallel with bucketed RCCL gradient all-reduce
 """
 __all__ = ["FastSCNN", "get_fast_scnn"]

@@ -14,7 +14,7 @@ DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 
 c_int, c_ll, c_float, c_vp, c_char_p = (ctypes.c_int, ctypes.c_longlong, ctypes.c_float,
                                         ctypes.c_void_p, ctypes.c_char_p)
-c_ull = ctypes.c_ulonglong
+c_ull, c_double = ctypes.c_ulonglong, ctypes.c_double
 P_int, P_ll, P_vp = ctypes.POINTER(c_int), ctypes.POINTER(c_ll), ctypes.POINTER(c_vp)
 
 # name -> (restype, argtypes)
@@ -87,6 +87,10 @@ SIGNATURES = {
                              c_vp]),
     "fscnn_sgd": (c_int, [c_vp, c_vp, c_vp, c_ll, c_float, c_float, c_float, c_float, c_int,
                           c_int, c_float, c_vp]),
+    "fscnn_adamw": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_ll, c_double, c_double, c_double,
+                            c_double, c_double, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp]),
+    "fscnn_adamw_segments": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_int,
+                                     c_vp, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp]),
     "fscnn_conv0_fwd": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp,
                                 c_int, c_vp]),
     "fscnn_conv0_wgrad_slab_floats": (c_ll, [c_int, c_int, c_int]),

@@ -655,6 +655,41 @@ int fscnn_sgd(float* p, const float* g, float* buf, long long n, float lr, float
   a.grad_scale = grad_scale;
   return sgd(a, S(stream));
 }
+int fscnn_adamw(float* p, const float* g, float* exp_avg, float* exp_avg_sq,
+                float* max_exp_avg_sq, long long n, double lr, double beta1, double beta2,
+                double eps, double weight_decay, int amsgrad, int maximize, float* step, int tick,
+                const float* grad_scale, const float* found_inf, void* stream) {
+  AdamwArgs a{};
+  a.n = n; a.p = p; a.g = g; a.m = exp_avg; a.v = exp_avg_sq; a.vmax = max_exp_avg_sq;
+  a.h = adamw_hyper(lr, beta1, beta2, eps, weight_decay, amsgrad, maximize, 0);
+  a.step = step; a.tick = tick; a.grad_scale = grad_scale; a.found_inf = found_inf;
+  return adamw(a, S(stream));
+}
+static_assert(sizeof(fscnn_adamw_seg) == sizeof(AdamwSeg) && FSCNN_ADAMW_CHUNK == ADAMW_CHUNK &&
+              FSCNN_ADAMW_MAX_GROUPS == ADAMW_MAXGROUPS, "fastscnn.h and kernels.hpp disagree");
+int fscnn_adamw_segments(float* p, const float* g, float* exp_avg, float* exp_avg_sq,
+                         float* max_exp_avg_sq, const fscnn_adamw_seg* segs,
+                         const fscnn_adamw_seg* host_segs, int nseg, const int* chunk_seg,
+                         int nchunks, const fscnn_adamw_group* groups, int ngroups, float* steps,
+                         int nslots, int tick, const float* grad_scale, const float* found_inf,
+                         void* stream) {
+  if (ngroups < 1 || ngroups > ADAMW_MAXGROUPS || !groups) {
+    set_error("fscnn_adamw_segments: %d groups (1..%d per launch)", ngroups, ADAMW_MAXGROUPS);
+    return E_INVALID;
+  }
+  AdamwSegArgs a{};
+  a.p = p; a.g = g; a.m = exp_avg; a.v = exp_avg_sq; a.vmax = max_exp_avg_sq;
+  a.segs = reinterpret_cast<const AdamwSeg*>(segs); a.chunk_seg = chunk_seg;
+  a.nseg = nseg; a.nchunks = nchunks; a.ngroups = ngroups;
+  for (int k = 0; k < ngroups; ++k) {
+    const fscnn_adamw_group& g = groups[k];
+    a.h[k] = adamw_hyper(g.lr, g.beta1, g.beta2, g.eps, g.weight_decay, g.amsgrad, g.maximize,
+                         g.step_slot);
+  }
+  a.steps = steps; a.nslots = nslots; a.tick = tick;
+  a.grad_scale = grad_scale; a.found_inf = found_inf;
+  return adamw_segments(a, reinterpret_cast<const AdamwSeg*>(host_segs), S(stream));
+}
 
 int fscnn_conv0_fwd(const void* x, int x_dtype, int N, int H, int W, const float* w,
                     const float* scale, const float* shift, int relu, void* y, int y_dtype,

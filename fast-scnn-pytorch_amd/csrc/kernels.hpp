@@ -406,6 +406,40 @@ struct SgdArgs {
   float grad_scale;  // multiply g first (e.g. 1/world_size); 1 = none
 };
 
+// AdamW (misc.hip; torch.optim.AdamW, train_bdd100k.py:183-188).  One group's hyperparameters as
+// the kernels take them by value: the per-element fp32 constants are rounded on the host from
+// double exactly as torch rounds its Python scalars; what the bias corrections need stays double
+// because they depend on the device-resident step.
+constexpr int ADAMW_MAXGROUPS = 8;
+constexpr int ADAMW_CHUNK = 2048;  // elements per workgroup (= FSCNN_ADAMW_CHUNK)
+struct AdamwHyper {
+  double lr, ln_b1, ln_b2;         // ln(beta): 1 - beta^t = -expm1(t * ln(beta))
+  float decay;                     // 1 - lr * weight_decay
+  float b1, omb1, b2, omb2, eps;   // omb = 1 - beta
+  int amsgrad, maximize, slot;     // slot: index of the group's step in `steps`
+};
+AdamwHyper adamw_hyper(double lr, double beta1, double beta2, double eps, double weight_decay,
+                       int amsgrad, int maximize, int slot);
+struct AdamwSeg {                  // = fscnn_adamw_seg
+  long long begin, end;            // arena elements; begin is a multiple of 16
+  int group;                       // index into the launch's groups
+  int chunk0;                      // first ADAMW_CHUNK-element chunk (workgroup) of the segment
+};
+struct AdamwArgs {                 // span form
+  long long n;
+  float* p; const float* g; float* m; float* v; float* vmax;
+  AdamwHyper h;
+  float* step; int tick;           // *step: applied steps so far; tick: advance it afterwards
+  const float* grad_scale; const float* found_inf;  // device scalars or null
+};
+struct AdamwSegArgs {              // segment form
+  float* p; const float* g; float* m; float* v; float* vmax;
+  const AdamwSeg* segs; const int* chunk_seg; int nseg, nchunks;
+  AdamwHyper h[ADAMW_MAXGROUPS]; int ngroups;
+  float* steps; int nslots, tick;  // tick: advance steps[0, nslots) after the update
+  const float* grad_scale; const float* found_inf;
+};
+
 // ---- launchers ----------------------------------------------------------------------------
 // fused stride-1 inverted-residual block, inference (ir.hip; models/fast_scnn.py:95-115)
 struct IrArgs {
@@ -677,6 +711,9 @@ int col2im3(const Col2ImArgs& a, int dtype, hipStream_t st);
 // *p = v (one thread): per-call scalars that captured graphs read from device memory
 int set_u64(uint64_t* p, uint64_t v, hipStream_t st);
 int sgd(const SgdArgs& a, hipStream_t st);
+int adamw(const AdamwArgs& a, hipStream_t st);
+// hsegs: host copy of a.segs (validated against ngroups / nchunks), or null
+int adamw_segments(const AdamwSegArgs& a, const AdamwSeg* hsegs, hipStream_t st);
 int cast_f32_bf16(const float* x, void* y, long long n, hipStream_t st);
 // per-step weight operands from the fp32 arena: plain casts and zero-padded transposes (misc.hip)
 constexpr int PREP_MAXJOBS = 48;

@@ -701,6 +701,246 @@ int sgd(const SgdArgs& a, hipStream_t st) {
   return check_launch("sgd");
 }
 
+// ---- fused AdamW over flat fp32 arenas ----------------------------------------------------
+// torch.optim.AdamW's single-tensor rule per element (train_bdd100k.py:183-188):
+//   g = ±grad (/ *grad_scale);  p *= 1 - lr*wd;  m = lerp(m, g, 1-b1);  v = b2*v + (1-b2)*g*g;
+//   amsgrad: vmax = max(vmax, v), used for v below;
+//   p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps),  t = *step + 1.
+// The step lives on the device (fp32, exact to 2^24) so that a GradScaler skip (*found_inf != 0:
+// nothing changes, the step included) needs no host read.  The update computes with step + 1 and
+// a one-thread launch behind it advances the step: no workgroup reads a step that another
+// launch's thread is writing.  The bias corrections are formed in double from the double
+// hyperparameters, once per thread behind the loads, and rounded to fp32 as torch rounds its
+// Python scalars; the per-element constants were rounded on the host the same way.
+// One workgroup per ADAMW_CHUNK elements: a thread's two 16-B accesses per array are independent
+// loads issued together; the partial last chunk of a span or segment takes 4-B accesses.
+// Memory-bound: 28 B per element (36 with amsgrad), plain vector stores.
+AdamwHyper adamw_hyper(double lr, double beta1, double beta2, double eps, double weight_decay,
+                       int amsgrad, int maximize, int slot) {
+  AdamwHyper h{};
+  h.lr = lr; h.ln_b1 = log(beta1); h.ln_b2 = log(beta2);  // log(0) = -inf: 1 - 0^t = 1
+  h.decay = (float)(1.0 - lr * weight_decay);
+  h.b1 = (float)beta1; h.omb1 = (float)(1.0 - beta1);
+  h.b2 = (float)beta2; h.omb2 = (float)(1.0 - beta2);
+  h.eps = (float)eps; h.amsgrad = amsgrad; h.maximize = maximize; h.slot = slot;
+  return h;
+}
+
+struct AdamwStep {  // the step-dependent constants of one launch's group
+  float neg_step_size, bc2_sqrt, gscale;
+};
+__device__ __forceinline__ AdamwStep adamw_step_consts(const AdamwHyper& h, float step,
+                                                       const float* grad_scale) {
+  const double t = (double)step + 1.0;
+  AdamwStep c;
+  c.neg_step_size = (float)(-h.lr / -expm1(t * h.ln_b1));
+  c.bc2_sqrt = (float)sqrt(-expm1(t * h.ln_b2));
+  c.gscale = grad_scale ? *grad_scale : 0.f;  // 0: no unscaling
+  return c;
+}
+__device__ __forceinline__ void adamw_elem(float& p, float g, float& m, float& v, float& vmax,
+                                           const AdamwHyper& h, const AdamwStep& c) {
+  // no fma contraction: every product and sum rounds once, as torch's separate tensor ops do
+  // (mul_, addcmul_, sqrt, div, add_, addcdiv_, in their operand order), and the span and segment
+  // kernels give the same bits whichever access path an element takes.  The one fma is lerp_'s
+  // own: ATen evaluates both of its forms as fmadd(weight, end - self, base).
+#pragma clang fp contract(off)
+  if (c.gscale != 0.f) g = g / c.gscale;
+  if (h.maximize) g = -g;
+  p *= h.decay;
+  m = h.omb1 < 0.5f ? fmaf(h.omb1, g - m, m) : fmaf(h.omb1 - 1.f, g - m, g);
+  v = h.b2 * v + (h.omb2 * g) * g;
+  float d = v;
+  if (h.amsgrad) d = vmax = fmaxf(vmax, v);
+  p += (c.neg_step_size * m) / (sqrtf(d) / c.bc2_sqrt + h.eps);
+}
+
+// [0, len) of the arrays (already offset to the chunk).  VEC: every pointer 16-B aligned.
+template <bool VEC>
+__device__ __forceinline__ void adamw_chunk(float* p, const float* g, float* m, float* v, float* vmax,
+                                            int len, const AdamwHyper& h, float step,
+                                            const float* grad_scale) {
+  constexpr int PER = ADAMW_CHUNK / 256 / 4;  // float4 per thread
+  const bool ams = h.amsgrad != 0;
+  if (VEC && len == ADAMW_CHUNK) {
+    float4 P[PER], G[PER], M[PER], V[PER], X[PER];
+#pragma unroll
+    for (int e = 0; e < PER; ++e) {
+      const int i = threadIdx.x * 4 + e * 1024;
+      P[e] = *reinterpret_cast<const float4*>(p + i);
+      G[e] = *reinterpret_cast<const float4*>(g + i);
+      M[e] = *reinterpret_cast<const float4*>(m + i);
+      V[e] = *reinterpret_cast<const float4*>(v + i);
+      X[e] = ams ? *reinterpret_cast<const float4*>(vmax + i) : float4{0.f, 0.f, 0.f, 0.f};
+    }
+    const AdamwStep c = adamw_step_consts(h, step, grad_scale);
+#pragma unroll
+    for (int e = 0; e < PER; ++e) {
+      const int i = threadIdx.x * 4 + e * 1024;
+      adamw_elem(P[e].x, G[e].x, M[e].x, V[e].x, X[e].x, h, c);
+      adamw_elem(P[e].y, G[e].y, M[e].y, V[e].y, X[e].y, h, c);
+      adamw_elem(P[e].z, G[e].z, M[e].z, V[e].z, X[e].z, h, c);
+      adamw_elem(P[e].w, G[e].w, M[e].w, V[e].w, X[e].w, h, c);
+      *reinterpret_cast<float4*>(p + i) = P[e];
+      *reinterpret_cast<float4*>(m + i) = M[e];
+      *reinterpret_cast<float4*>(v + i) = V[e];
+      if (ams) *reinterpret_cast<float4*>(vmax + i) = X[e];
+    }
+    return;
+  }
+  constexpr int SPER = ADAMW_CHUNK / 256;
+  float P[SPER], G[SPER], M[SPER], V[SPER], X[SPER];
+#pragma unroll
+  for (int e = 0; e < SPER; ++e) {
+    const int i = threadIdx.x + 256 * e;
+    const bool in = i < len;
+    P[e] = in ? p[i] : 0.f;
+    G[e] = in ? g[i] : 0.f;
+    M[e] = in ? m[i] : 0.f;
+    V[e] = in ? v[i] : 0.f;
+    X[e] = in && ams ? vmax[i] : 0.f;
+  }
+  const AdamwStep c = adamw_step_consts(h, step, grad_scale);
+#pragma unroll
+  for (int e = 0; e < SPER; ++e) {
+    const int i = threadIdx.x + 256 * e;
+    if (i >= len) break;
+    adamw_elem(P[e], G[e], M[e], V[e], X[e], h, c);
+    p[i] = P[e];
+    m[i] = M[e];
+    v[i] = V[e];
+    if (ams) vmax[i] = X[e];
+  }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void adamw_kernel(AdamwArgs a) {
+  if (a.found_inf && *a.found_inf != 0.f) return;
+  const long long base = (long long)blockIdx.x * ADAMW_CHUNK;
+  const int len = blockIdx.x + 1 < gridDim.x ? ADAMW_CHUNK : (int)(a.n - base);  // 32-bit test
+  adamw_chunk<VEC>(a.p + base, a.g + base, a.m + base, a.v + base, a.vmax ? a.vmax + base : nullptr,
+                   len, a.h, *a.step, a.grad_scale);
+}
+
+// One launch over every run of every group.  Workgroup b works on chunk b of the flattened
+// segment list: chunk_seg[b] names its segment (one uniform lookup, as weights_prep_kernel's
+// cstart search), segs[] its element range and group, a.h[group] the hyperparameters.
+// Nothing outside [begin, end) of a segment is read or written.
+__global__ __launch_bounds__(256) void adamw_segments_kernel(AdamwSegArgs a) {
+  if (a.found_inf && *a.found_inf != 0.f) return;
+  const int b = blockIdx.x;
+  const int s = a.chunk_seg[b];
+  if ((unsigned)s >= (unsigned)a.nseg) return;
+  const AdamwSeg sg = a.segs[s];
+  if ((unsigned)sg.group >= (unsigned)a.ngroups) return;
+  const AdamwHyper& h = a.h[sg.group];
+  // 32-bit arithmetic within a segment (host-checked, as weights_prep's jobs).  A 64-bit
+  // min(ADAMW_CHUNK, end - base) here was compiled to a select on the wrong condition (the scalar
+  // condition code of the amsgrad test that follows): groups without amsgrad ran whole chunks
+  // over their segments' ends.
+  const int n = (int)(sg.end - sg.begin);
+  const int off = (b - sg.chunk0) * ADAMW_CHUNK;
+  if (off < 0 || off >= n) return;
+  const int len = n - off < ADAMW_CHUNK ? n - off : ADAMW_CHUNK;
+  const long long base = sg.begin + off;
+  adamw_chunk<true>(a.p + base, a.g + base, a.m + base, a.v + base,
+                    a.vmax ? a.vmax + base : nullptr, len, h, a.steps[h.slot], a.grad_scale);
+}
+
+// steps[0, n) += 1 unless *found_inf (one thread, stream-ordered behind the update)
+__global__ void adamw_tick_kernel(float* steps, int n, const float* found_inf) {
+  if (found_inf && *found_inf != 0.f) return;
+  for (int i = 0; i < n; ++i) steps[i] += 1.f;
+}
+
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+int adamw(const AdamwArgs& a, hipStream_t st) {
+  if (a.n < 0) {
+    set_error("adamw: n=%lld", a.n);
+    return E_INVALID;
+  }
+  if (!a.p || !a.g || !a.m || !a.v || !a.step || (a.h.amsgrad && !a.vmax)) {
+    set_error("adamw: null p / g / exp_avg / exp_avg_sq / step%s",
+              a.h.amsgrad ? " / max_exp_avg_sq (amsgrad)" : "");
+    return E_INVALID;
+  }
+  if (a.n > 0) {
+    const long long grid = (a.n + ADAMW_CHUNK - 1) / ADAMW_CHUNK;
+    if (grid > 0x7fffffffLL) {
+      set_error("adamw: n=%lld is more than one launch takes", a.n);
+      return E_INVALID;
+    }
+    const bool vec = aligned16(a.p) && aligned16(a.g) && aligned16(a.m) && aligned16(a.v) &&
+                     (!a.h.amsgrad || aligned16(a.vmax));
+    AdamwArgs k = a;
+    if (!k.h.amsgrad) k.vmax = nullptr;
+    if (vec) prof_launch(adamw_kernel<true>, (unsigned)grid, 256, 0, st, k);
+    else prof_launch(adamw_kernel<false>, (unsigned)grid, 256, 0, st, k);
+  }
+  if (a.tick) prof_launch(adamw_tick_kernel, 1, 1, 0, st, a.step, 1, a.found_inf);
+  return check_launch("adamw");
+}
+
+int adamw_segments(const AdamwSegArgs& a, const AdamwSeg* hsegs, hipStream_t st) {
+  if (a.ngroups < 1 || a.ngroups > ADAMW_MAXGROUPS) {
+    set_error("adamw_segments: %d groups (1..%d per launch)", a.ngroups, ADAMW_MAXGROUPS);
+    return E_INVALID;
+  }
+  if (a.nseg < 0 || a.nchunks < 0 || a.nslots < 1) {
+    set_error("adamw_segments: nseg=%d nchunks=%d nslots=%d", a.nseg, a.nchunks, a.nslots);
+    return E_INVALID;
+  }
+  bool ams = false;
+  for (int k = 0; k < a.ngroups; ++k) {
+    ams = ams || a.h[k].amsgrad;
+    if (a.h[k].slot < 0 || a.h[k].slot >= a.nslots) {
+      set_error("adamw_segments: group %d has step slot %d of %d", k, a.h[k].slot, a.nslots);
+      return E_INVALID;
+    }
+  }
+  if (!a.p || !a.g || !a.m || !a.v || !a.steps || (ams && !a.vmax) ||
+      (a.nchunks > 0 && (!a.segs || !a.chunk_seg))) {
+    set_error("adamw_segments: null p / g / exp_avg / exp_avg_sq / steps / table%s",
+              ams ? " / max_exp_avg_sq (amsgrad)" : "");
+    return E_INVALID;
+  }
+  if (!aligned16(a.p) || !aligned16(a.g) || !aligned16(a.m) || !aligned16(a.v) ||
+      (ams && !aligned16(a.vmax))) {
+    set_error("adamw_segments: the arenas must be 16-byte aligned");
+    return E_INVALID;
+  }
+  if (hsegs) {
+    int chunk = 0;
+    for (int s = 0; s < a.nseg; ++s) {
+      const AdamwSeg& g = hsegs[s];
+      if (g.group < 0 || g.group >= a.ngroups) {
+        set_error("adamw_segments: segment %d names group %d of %d", s, g.group, a.ngroups);
+        return E_INVALID;
+      }
+      if (g.begin < 0 || g.end < g.begin || g.end - g.begin >= (1LL << 31) || (g.begin & 15) ||
+          g.chunk0 != chunk) {
+        set_error("adamw_segments: segment %d [%lld, %lld) chunk0 %d (expected %d)", s, g.begin,
+                  g.end, g.chunk0, chunk);
+        return E_INVALID;
+      }
+      const long long c = (g.end - g.begin + ADAMW_CHUNK - 1) / ADAMW_CHUNK;
+      if (c > a.nchunks - chunk) {
+        set_error("adamw_segments: segments cover more than nchunks=%d chunks", a.nchunks);
+        return E_INVALID;
+      }
+      chunk += (int)c;
+    }
+    if (chunk != a.nchunks) {
+      set_error("adamw_segments: segments cover %d chunks, nchunks=%d", chunk, a.nchunks);
+      return E_INVALID;
+    }
+  }
+  if (a.nchunks > 0) prof_launch(adamw_segments_kernel, (unsigned)a.nchunks, 256, 0, st, a);
+  if (a.tick) prof_launch(adamw_tick_kernel, 1, 1, 0, st, a.steps, a.nslots, a.found_inf);
+  return check_launch("adamw_segments");
+}
+
 // ---- per-step weight preparation ---------------------------------------------------------------
 // One launch builds the compute-dtype weight operands of a training step from the fp32 master
 // arena P: the plain cast of the whole arena (bf16 steps) and, for every dense conv, W^T

@@ -22,6 +22,8 @@
  *   fscnn_ce_fwd / fscnn_ce_bwd                   nn.CrossEntropyLoss(ignore_index=-1)
  *                                                 (utils/loss.py:103-124, train.py:191)
  *   fscnn_sgd                                     torch.optim.SGD.step (train.py:195-198,274)
+ *   fscnn_adamw / fscnn_adamw_segments            torch.optim.AdamW.step under GradScaler
+ *                                                 (train_bdd100k.py:183-188, 258-266)
  *   fscnn_conv0_fwd                               _ConvBNReLU(3,32,3,2) (models/fast_scnn.py:153)
  *   fscnn_dw3x3_*                                 nn.Conv2d(groups=C, k=3, pad=1) (:70, :86)
  *   fscnn_pw_gemm / fscnn_pw_wgrad                nn.Conv2d(k=1) (:73, :103, :107, :124-128,
@@ -400,6 +402,50 @@ int fscnn_ce_bwd(const void* logits, int dtype, const long long* target, int N, 
 int fscnn_sgd(float* p, const float* g, float* buf, long long n, float lr, float momentum,
               float dampening, float weight_decay, int nesterov, int first, float grad_scale,
               void* stream);
+
+/* torch.optim.AdamW.step (train_bdd100k.py:183-188, 258-266) in fp32, element by element:
+ *   g = grad (negated if maximize; divided by *grad_scale if given);  p *= 1 - lr * weight_decay;
+ *   m += (g - m) * (1 - beta1);  v = beta2 * v + (1 - beta2) * g * g;
+ *   amsgrad: vmax = max(vmax, v), used in place of v;
+ *   p -= lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps),  t = step + 1.
+ * The step count is a device fp32 scalar.  grad_scale / found_inf are device fp32 scalars or
+ * null (what torch.amp.GradScaler hands an optimizer): when *found_inf != 0 the call changes
+ * nothing, the step included; otherwise the step advances by one, in a one-thread launch behind
+ * the update when `tick` is set (clear it on all but the last call that shares a step).
+ * max_exp_avg_sq may be null unless amsgrad.
+ *
+ * fscnn_adamw: one span of n >= 0 elements, any 4-byte alignment. */
+int fscnn_adamw(float* p, const float* g, float* exp_avg, float* exp_avg_sq,
+                float* max_exp_avg_sq, long long n, double lr, double beta1, double beta2,
+                double eps, double weight_decay, int amsgrad, int maximize, float* step, int tick,
+                const float* grad_scale, const float* found_inf, void* stream);
+/* fscnn_adamw_segments: one launch over every run of every parameter group of 16-byte aligned
+ * arenas that share their offsets.  segs (device; host_segs: the same table in host memory, checked
+ * when not null): nseg segments [begin, end) in elements, fewer than 2^31 each, begin a multiple
+ * of 16, each with its index into `groups` and chunk0, the sum of
+ * ceil((end - begin) / FSCNN_ADAMW_CHUNK) over the segments before it.  chunk_seg (device): for
+ * each of the nchunks chunks its segment.  Elements
+ * outside every segment are neither read nor written.  groups: up to FSCNN_ADAMW_MAX_GROUPS, read
+ * from host memory at the call (nothing to upload when lr changes); step_slot indexes `steps`
+ * (nslots device floats), all of which advance when `tick` is set. */
+#define FSCNN_ADAMW_CHUNK 2048
+#define FSCNN_ADAMW_MAX_GROUPS 8
+typedef struct fscnn_adamw_seg {
+  long long begin, end;
+  int group;
+  int chunk0;
+} fscnn_adamw_seg;
+typedef struct fscnn_adamw_group {
+  double lr, beta1, beta2, eps, weight_decay;
+  int amsgrad, maximize;
+  int step_slot;
+} fscnn_adamw_group;
+int fscnn_adamw_segments(float* p, const float* g, float* exp_avg, float* exp_avg_sq,
+                         float* max_exp_avg_sq, const fscnn_adamw_seg* segs,
+                         const fscnn_adamw_seg* host_segs, int nseg, const int* chunk_seg,
+                         int nchunks, const fscnn_adamw_group* groups, int ngroups, float* steps,
+                         int nslots, int tick, const float* grad_scale, const float* found_inf,
+                         void* stream);
 
 /* ---- individual kernels (per-op parity tests) ------------------------- */
 int fscnn_conv0_fwd(const void* x, int x_dtype, int N, int H, int W, const float* w,
