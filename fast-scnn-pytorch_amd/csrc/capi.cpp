@@ -391,6 +391,52 @@ int fscnn_predict(const fscnn_plan* plan, const void* x, int x_dtype, void* labe
   GUARD(net_forward(plan->plan, r));
 }
 
+long long fscnn_validate_ws_bytes(const fscnn_plan* plan) {
+  if (!plan || plan->plan.train) {
+    set_error("fscnn_validate_ws_bytes: the validation head needs an inference plan (train=0)");
+    return E_INVALID;
+  }
+  const Plan& pl = plan->plan;
+  return (long long)eval_head_parts(pl.N, pl.H, pl.W) * 4 * (long long)sizeof(float);
+}
+
+int fscnn_validate(const fscnn_plan* plan, const void* x, int x_dtype, const long long* target,
+                   int head, long long ignore_index, float smooth, float dice_weight,
+                   float focal_weight, float alpha, float gamma, float aux_weight, float* loss,
+                   long long* counts, const float* params, float* running, long long* nbt,
+                   void* ws, void* head_ws, void* stream) {
+  if (!plan || !x || !target || !loss || !params || !running || !ws || !head_ws) {
+    set_error("fscnn_validate: null argument");
+    return E_INVALID;
+  }
+  const Plan& pl = plan->plan;
+  if (pl.train) {
+    set_error("fscnn_validate: needs an inference plan (train=0)");
+    return E_INVALID;
+  }
+  if (head != HEAD_CE && head != HEAD_DICE) {
+    set_error("fscnn_validate: head %d (0 cross entropy, 1 dice)", head);
+    return E_INVALID;
+  }
+  if (aux_weight != 0.f && !pl.net->aux) {
+    set_error("fscnn_validate: aux_weight without an aux net");
+    return E_INVALID;
+  }
+  if (!eval_head_ok(pl.N, pl.net->num_classes, pl.H3, pl.W3, pl.H, pl.W, head == HEAD_DICE)) {
+    set_error("fscnn_validate: the validation head does not take this geometry (C=%d, %dx%d from "
+              "%dx%d)", pl.net->num_classes, pl.H, pl.W, pl.H3, pl.W3);
+    return E_UNSUPPORTED;
+  }
+  RunArgs r{};
+  r.x = x; r.x_dtype = x_dtype; r.out = nullptr; r.out_dtype = pl.dtype;
+  r.P = params; r.R = running; r.NBT = nbt; r.ws = ws; r.momentum = 0.1f; r.st = S(stream);
+  r.validate = 1; r.target = target; r.ignore_index = ignore_index; r.loss2 = loss;
+  r.head = head; r.smooth = smooth; r.dice_weight = dice_weight; r.focal_weight = focal_weight;
+  r.alpha = alpha; r.gamma = gamma; r.aux_weight = aux_weight;
+  r.counts = reinterpret_cast<unsigned long long*>(counts); r.head_ws = head_ws;
+  GUARD(net_forward(plan->plan, r));
+}
+
 int fscnn_seg_metric(const void* pred, int pred_dtype, const long long* target, long long n,
                      int nclass, long long* counts, void* stream) {
   if ((!pred || !target || !counts) && n > 0) {

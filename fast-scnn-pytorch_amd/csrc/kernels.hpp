@@ -369,6 +369,26 @@ struct DiceHeadArgs {
   const double* stats = nullptr;  // (I, S, T, F), written by the finalize
 };
 
+// Fused validation head (evalhead.hip): upsample + criterion loss + SegmentationMetric counters
+// from the low-res logits of an inference plan; no full-resolution tensor is written.
+struct EvalHeadArgs {
+  int N, C, Hl, Wl, H, W;
+  const void* logits;        // NHWC [N][Hl][Wl][ldl]
+  int ldl;
+  const long long* target;   // [N][H][W]
+  long long ignore_index = -1;  // CE: pixels left out of the mean
+  int dice = 0;              // 0: CE sums (loss, count); 1: Dice sums (I, S, T, F)
+  int focal = 0;
+  float alpha = 0.5f, gamma = 2.f;
+  float smooth = 1e-6f, wd = 1.f, wf = 0.f;
+  unsigned long long* counts = nullptr;  // [2 + 3C] accumulated (seg_metric's layout), or null
+  float* part = nullptr;     // [eval_head_parts][4]
+  float* loss = nullptr;     // device scalar: (accumulate ? loss : 0) + weight * value
+  float weight = 1.f;
+  int accumulate = 0;
+  int tvec = 0;              // (set by eval_head) the target rows take 16-byte loads
+};
+
 struct DropArgs {
   int N, H, W, C;
   const void* x; int ldx;
@@ -690,6 +710,11 @@ int dice_head(const DiceHeadArgs& a, void* head_ws, float* loss, double* stats, 
 int dice_head_scale(const void* head_ws, void* g, long long M, int C, int ld, const float* gout,
                     const double* stats, float smooth, float wd, float wf, double npix, int dtype,
                     hipStream_t st);
+// Validation head: eval_head_ok tells whether the kernel takes the geometry (staged rows in LDS,
+// 1 .. 32 classes, Dice from 2); eval_head returns E_UNSUPPORTED otherwise
+int eval_head_parts(int N, int H, int W);
+bool eval_head_ok(int N, int C, int Hl, int Wl, int H, int W, int dice);
+int eval_head(const EvalHeadArgs& a, int dtype, hipStream_t st);
 int dropout(const DropArgs& a, int dtype, hipStream_t st);
 // GPU input path: ToTensor + Normalize of uint8 HWC images into NCHW (fp32 / bf16)
 int normalize_u8(const uint8_t* x, int N, int H, int W, const float* mean, const float* std,

@@ -1346,6 +1346,21 @@ struct Exec {
       TRY(gemm_nt(g, dt, r.st));
     }
     if (net.aux && r.aux_out) TRY(forward_aux());
+    if (r.validate) {
+      // ---- fused validation head: loss + metric counters from the low-res logits ----
+      if (train) {
+        set_error("validate needs an inference plan (train=0)");
+        return E_INVALID;
+      }
+      g_prof_tag = "head (upsample + loss + metric)";
+      TRY(eval_head(eval_head_args(W(pl.logits), 1.f, 0, r.counts), dt, r.st));
+      if (net.aux && r.aux_weight != 0.f) {  // loss only: the counters come from output 0
+        TRY(forward_aux(false));
+        g_prof_tag = "auxlayer head (upsample + loss)";
+        TRY(eval_head(eval_head_args(W(pl.aux_logits), r.aux_weight, 1, nullptr), dt, r.st));
+      }
+      return OK;
+    }
     if (r.target) {
       // ---- fused training head: upsample + CE + gradient at low resolution ----
       if (!train || frozen) {
@@ -1466,7 +1481,8 @@ struct Exec {
   }
 
   // aux head (models/fast_scnn.py:24-31,42-45) on the LearningToDownsample output l2pw.a
-  int forward_aux() {
+  // (upsample = false: stop at the low-res aux logits, which the validation head reads)
+  int forward_aux(bool upsample = true) {
     const Unit& u = pl.aux0;
     Im2ColArgs ic{};
     ic.N = pl.N; ic.H = pl.H3; ic.W = pl.W3; ic.C = 64; ic.x = W(pl.l2pw.a); ic.ldx = 64;
@@ -1487,10 +1503,26 @@ struct Exec {
     g.B = Wg(net.aux4); g.ldb = 32; g.shift = P(net.aux4.b);
     g.C = W(pl.aux_logits); g.ldc = pl.Cp;
     TRY(gemm_nt(g, dt, r.st));
+    if (!upsample) return OK;
     UpArgs up{};
     up.N = pl.N; up.Hi = pl.H3; up.Wi = pl.W3; up.C = net.num_classes; up.Ho = pl.H; up.Wo = pl.W;
     up.x = W(pl.aux_logits); up.ldx = pl.Cp; up.y = r.aux_out; up.ldy = 0;
     return up_nchw(up, dt, r.out_dtype, r.st);
+  }
+
+  // the validation head over one set of low-res logits: loss2[0] = (accumulate ? loss2[0] : 0) +
+  // weight * criterion; counts (or null): the metric counters of its argmax
+  EvalHeadArgs eval_head_args(const void* logits, float weight, int accumulate,
+                              unsigned long long* counts) const {
+    EvalHeadArgs h{};
+    h.N = pl.N; h.C = net.num_classes; h.Hl = pl.H3; h.Wl = pl.W3; h.H = pl.H; h.W = pl.W;
+    h.logits = logits; h.ldl = pl.Cp; h.target = r.target; h.ignore_index = r.ignore_index;
+    h.dice = r.head == HEAD_DICE; h.focal = r.focal_weight != 0.f;
+    h.alpha = r.alpha; h.gamma = r.gamma;
+    h.smooth = r.smooth; h.wd = r.dice_weight; h.wf = r.focal_weight;
+    h.counts = counts; h.part = (float*)r.head_ws; h.loss = r.loss2;
+    h.weight = weight; h.accumulate = accumulate;
+    return h;
   }
 
   // aux head backward from d(aux_out); its input gradient is added into l2pw.ga (which the FFM
@@ -2086,7 +2118,8 @@ std::vector<uint64_t> run_key(int kind, int s0, int s1, const RunArgs& r) {
           P(r.bws), P(r.dout), P(r.daux), fbits(r.dropout_p), fbits(r.momentum), P(r.target),
           (uint64_t)r.ignore_index, P(r.loss2), P(r.gloss), P(r.dx), (uint64_t)r.dx_dtype,
           (uint64_t)r.head, fbits(r.smooth), fbits(r.dice_weight), fbits(r.focal_weight),
-          fbits(r.alpha), fbits(r.gamma), P(r.head_ws), P(r.dice_stats)};
+          fbits(r.alpha), fbits(r.gamma), P(r.head_ws), P(r.dice_stats), (uint64_t)r.validate,
+          fbits(r.aux_weight), P(r.counts)};
 }
 
 template <typename F>
@@ -2171,11 +2204,11 @@ int net_forward_impl(const Plan& pl, const RunArgs& r) {
     set_error("fscnn_forward: input / output dtype codes must be 0 (fp32), 1 (bf16) or 2 (fp16)");
     return E_INVALID;
   }
-  if (pl.net->aux && r.target) {
+  if (pl.net->aux && r.target && !r.validate) {
     set_error("forward_loss: the fused loss head covers the main output only (aux net)");
     return E_UNSUPPORTED;
   }
-  if (pl.net->aux && !r.aux_out && !r.labels) {
+  if (pl.net->aux && !r.aux_out && !r.labels && !r.validate) {
     set_error("fscnn_forward: this net has the aux head; use fscnn_forward_aux");
     return E_INVALID;
   }

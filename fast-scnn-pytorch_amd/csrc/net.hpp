@@ -174,6 +174,14 @@ struct RunArgs {
   // eval prediction: forward with labels != null writes argmax(upsampled logits) instead of out
   void* labels = nullptr;
   int label_u8 = 0;
+  // validation (inference plans): forward with validate != 0 ends in the fused eval head
+  // (evalhead.hip) instead of the upsample: loss2[0] = the criterion (head, target, ignore_index /
+  // the Dice scalars above) of the main output, plus aux_weight times that of the aux output when
+  // aux_weight != 0 (aux nets); counts (or null) accumulates the SegmentationMetric counters of
+  // argmax(main output); head_ws holds the partial records (eval_head_parts x 4 floats)
+  int validate = 0;
+  float aux_weight = 0.f;
+  unsigned long long* counts = nullptr;
   // backward: gradient of the input image, NCHW [N][3][H][W] in dx_dtype (autograd of x through
   // conv0, models/fast_scnn.py:153), or null
   void* dx = nullptr;

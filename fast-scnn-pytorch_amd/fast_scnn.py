@@ -230,6 +230,7 @@ class _Shared:
 
 
 MODE_EVAL, MODE_TRAIN, MODE_EVAL_GRAD = 0, 1, 2  # plan modes (include/fastscnn.h fscnn_plan_create)
+E_UNSUPPORTED = -2  # the library's "this kernel does not take the geometry" status
 
 
 class _FastSCNNFunction(torch.autograd.Function):
@@ -374,6 +375,7 @@ class FastSCNN(nn.Module):
         object.__setattr__(self, "_shared", _Shared())
         object.__setattr__(self, "_arena", None)
         object.__setattr__(self, "grad_stage_hook", None)
+        object.__setattr__(self, "_last_validate_fused", None)  # route of the last validate()
 
     # ---- arenas ----------------------------------------------------------------------------
     def native(self):
@@ -631,6 +633,116 @@ class FastSCNN(nn.Module):
         if getattr(self, "_keep_ws", False):
             self._debug = {"plan": plan, "ws": ws, "dt": dt}
         return labels
+
+    def validate(self, x, target, criterion=None, metric=None, ignore_index=-1):
+        """One batch of ``Trainer.validation`` (train.py:370-439): the loss ``criterion`` gives on
+        ``self(x)`` as a 0-dim fp32 device tensor, and ``metric.update(argmax(self(x)[0], 1),
+        target)`` added into ``metric`` (this package's ``SegmentationMetric``, or None for the
+        loss alone).  Requires ``model.eval()``; runs under ``no_grad``, touches no parameter or
+        running statistic and reads nothing back to the host.
+
+        Where the criterion has a fused head (``_head_spec``: None = cross entropy with
+        ``ignore_index``, the CE and Dice / Focal+Dice criteria of this package or the reference)
+        the forward ends in one kernel over the low-resolution logits that forms every upsampled
+        logit exactly as ``forward`` stores it and keeps only the loss sums and the counters: no
+        full-resolution logits, no labels.  A criterion with ``aux=True`` on an aux model adds
+        ``aux_weight`` times the aux output's loss (a second, loss-only pass).  A CE batch without
+        a valid pixel gives NaN, like the mean over no element.
+
+        Everything else -- the OHEM criterion, unknown criteria, geometries the head does not
+        take, ``FSCNN_VAL_FUSED=0`` -- computes the same two results by the unfused route,
+        ``criterion(self(x), target)`` (``self(x)[0]`` for the criteria that take a tensor) and
+        ``metric.update``.  ``_last_validate_fused`` records which route ran."""
+        if self.training:
+            raise RuntimeError("validate is the evaluation step; call model.eval() first")
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise RuntimeError("FastSCNN: expected input [N, 3, H, W], got %s" % (tuple(x.shape),))
+        if not x.is_cuda or not target.is_cuda:
+            raise RuntimeError("FastSCNN.validate: the HIP path needs ROCm device tensors")
+        N, _, H, W = x.shape
+        if tuple(target.shape) != (N, H, W):
+            raise RuntimeError("validate: target %s does not match input %s"
+                               % (tuple(target.shape), tuple(x.shape)))
+        if metric is not None and metric.nclass != self.num_classes:
+            raise RuntimeError("validate: metric counts %d classes, the model has %d"
+                               % (metric.nclass, self.num_classes))
+        with torch.no_grad():
+            loss = None
+            if os.environ.get("FSCNN_VAL_FUSED", "1") != "0":
+                try:
+                    spec = _head_spec(criterion, ignore_index)
+                except RuntimeError:  # no fused head for this criterion
+                    spec = None
+                if spec is not None:
+                    loss = self._validate_fused(x, target, criterion, spec, metric)
+            fused = loss is not None
+            if not fused:
+                loss = self._validate_unfused(x, target, criterion, metric, ignore_index)
+        self._last_validate_fused = fused
+        return loss
+
+    def _validate_fused(self, x, target, criterion, spec, metric):
+        """The fused route of ``validate``; None when the library does not take the geometry."""
+        nat = self.native()
+        ar = self._exec_arena(x.device)
+        N, _, H, W = x.shape
+        if H < 32 or W < 32:
+            raise RuntimeError("FastSCNN: input %dx%d too small (needs >= 32x32)" % (H, W))
+        dt = self._compute_dtype(x, False)
+        x = self._input(x)
+        target = target.to(torch.int64).contiguous()
+        from . import loss as _loss
+        dice = spec[0] == "dice"
+        if _loss.CHECK_TARGETS:
+            if dice:  # no ignore_index in Dice (forward_loss's check)
+                bad = (target < 0) | (target >= self.num_classes)
+                if bool(bad.any()):
+                    raise IndexError("Target %d is out of bounds." % int(target[bad].flatten()[0]))
+            else:
+                _loss.check_targets(target, self.num_classes, spec[1])
+        ignore = 0 if dice else spec[1]
+        smooth, dw, fw_, alpha, gamma = spec[1:] if dice else (1e-6, 1.0, 0.0, 0.5, 2.0)
+        aux_w = 0.0
+        if self.aux and criterion is not None and getattr(criterion, "aux", False):
+            aux_w = float(criterion.aux_weight)
+        plan, fw, _ = nat.plan(N, H, W, _lib.dtype_code(dt), False, x.device)
+        lib = _lib.load()
+        hb = int(lib.fscnn_validate_ws_bytes(plan))
+        if hb < 0:
+            _lib.check(hb, "fscnn_validate_ws_bytes")
+        ws = torch.empty(max(fw, 1), dtype=torch.uint8, device=x.device)
+        head_ws = torch.empty(max(hb, 1), dtype=torch.uint8, device=x.device)
+        loss = torch.empty(1, dtype=torch.float32, device=x.device)
+        counts = metric.device_counts(x.device) if metric is not None else None
+        with torch.cuda.device(x.device):
+            rc = lib.fscnn_validate(plan, _lib.ptr(x), _lib.dtype_code(x.dtype), _lib.ptr(target),
+                                    1 if dice else 0, int(ignore), _lib.c_float(smooth),
+                                    _lib.c_float(dw), _lib.c_float(fw_), _lib.c_float(alpha),
+                                    _lib.c_float(gamma), _lib.c_float(aux_w), _lib.ptr(loss),
+                                    _lib.ptr(counts), _lib.ptr(ar["P"]), _lib.ptr(ar["R"]),
+                                    _lib.ptr(ar["NBT"]), _lib.ptr(ws), _lib.ptr(head_ws),
+                                    _lib.stream_ptr(x.device))
+        if rc == E_UNSUPPORTED:  # nothing was launched: the geometry check comes first
+            return None
+        _lib.check(rc, "fscnn_validate")
+        if getattr(self, "_keep_ws", False):
+            self._debug = {"plan": plan, "ws": ws, "dt": dt}
+        return loss.reshape(())
+
+    def _validate_unfused(self, x, target, criterion, metric, ignore_index):
+        """The same two results from full-resolution logits (criteria without a fused head)."""
+        outs = self._run_forward(x, MODE_EVAL)[0]
+        if criterion is None:
+            from . import loss as _loss
+            loss = _loss.cross_entropy(outs[0], target, ignore_index)
+        else:
+            names = [c.__name__ for c in type(criterion).__mro__]
+            takes_tensor = "FocalDiceLoss" in names or (
+                "DiceLoss" in names and "MixDiceLoss" not in names)
+            loss = criterion(outs[0] if takes_tensor else outs, target)
+        if metric is not None:
+            metric.update(torch.argmax(outs[0], 1), target)
+        return loss.to(torch.float32).reshape(())
 
     def debug_buffer(self, name):
         """Tensor view of a named plan buffer of the last forward/backward (set ``_keep_ws``).

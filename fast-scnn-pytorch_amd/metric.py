@@ -46,6 +46,16 @@ class SegmentationMetric:
                   _lib.ptr(label), pred.numel(), self.nclass, _lib.ptr(self._counts),
                   _lib.stream_ptr(dev))
 
+    def device_counts(self, device):
+        """The int64 device tensor [2 + 3 * nclass] the counters accumulate in, allocated (zero)
+        on ``device`` at first use: ``FastSCNN.validate`` adds a batch's counts straight into it."""
+        if self._counts is None:
+            self._counts = torch.zeros(2 + 3 * self.nclass, dtype=torch.int64, device=device)
+        elif self._counts.device != torch.device(device):
+            raise RuntimeError("SegmentationMetric: counters on %s, batch on %s"
+                               % (self._counts.device, device))
+        return self._counts
+
     def counts(self):
         """[correct, labeled, inter[C], area_pred[C], area_lab[C]] accumulated so far (numpy)."""
         if self._counts is None:

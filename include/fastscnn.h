@@ -119,6 +119,26 @@ int fscnn_backward_aux(const fscnn_plan* plan, const void* dout, const void* dau
 int fscnn_predict(const fscnn_plan* plan, const void* x, int x_dtype, void* labels,
                   int label_dtype, const float* params, float* running, long long* nbt, void* ws,
                   void* stream);
+/* Validation step (Trainer.validation, train.py:370-439): forward of an inference plan that ends
+ * in one fused head over the low-resolution logits instead of the upsample.  It forms every
+ * full-resolution logit exactly as fscnn_forward stores it and leaves behind only
+ *   loss[0]  (device float) the criterion of the main output: head 0 = cross entropy with
+ *            ignore_index (NaN when no pixel is valid, like the mean over no element), head 1 =
+ *            the Dice / Focal+Dice loss with the scalars of fscnn_forward_loss_dice; on an aux
+ *            net with aux_weight != 0, plus aux_weight times the criterion of the aux output;
+ *   counts   (int64 [2 + 3*num_classes], ACCUMULATED; may be null) the fscnn_seg_metric
+ *            counters of argmax(main output) against target.
+ * No logits and no labels are written; two calls on the same inputs give the same bits.
+ * head_ws: fscnn_validate_ws_bytes(plan) bytes for the partial sums (negative, fscnn_last_error
+ * set, unless the plan is an inference plan).  Returns -1 for training plans and -2 for
+ * geometries the head does not take (num_classes above 32, Dice below 2, low-resolution rows
+ * that do not fit its LDS staging): use fscnn_forward + the unfused criterion there. */
+long long fscnn_validate_ws_bytes(const fscnn_plan* plan);
+int fscnn_validate(const fscnn_plan* plan, const void* x, int x_dtype, const long long* target,
+                   int head, long long ignore_index, float smooth, float dice_weight,
+                   float focal_weight, float alpha, float gamma, float aux_weight, float* loss,
+                   long long* counts, const float* params, float* running, long long* nbt,
+                   void* ws, void* head_ws, void* stream);
 /* SegmentationMetric counters (utils/metric.py:73-105, batch_pix_accuracy +
  * batch_intersection_union) of n predictions (pred_dtype 0 int64, 1 uint8) against int64 labels,
  * ACCUMULATED into counts[2 + 3*nclass] (int64): [correct, labeled, inter[C], area_pred[C],
