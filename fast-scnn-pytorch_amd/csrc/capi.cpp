@@ -51,10 +51,7 @@ struct ProfState {
 } g_prof;
 }  // namespace
 
-bool g_host_prof = [] {
-  const char* e = getenv("FSCNN_HOST_PROF");
-  return e && e[0] == '1';
-}();
+bool g_host_prof = env_on("FSCNN_HOST_PROF", false);
 namespace {
 struct HostProf {
   double us[4] = {0, 0, 0, 0};

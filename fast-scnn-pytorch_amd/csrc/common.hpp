@@ -11,6 +11,7 @@
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <type_traits>
 
 #include <string>
@@ -453,6 +454,24 @@ const char* last_error();
 int check_launch(const char* what);
 
 enum Status : int { OK = 0, E_INVALID = -1, E_UNSUPPORTED = -2, E_HIP = -3 };
+
+// ---- environment switches (each caller reads its switch once, through a function-local static) --
+// default-on switches: only a value starting with '0' turns them off; default-off switches: only
+// a value starting with '1' turns them on
+inline bool env_on(const char* name, bool dflt = true) {
+  const char* e = getenv(name);
+  return dflt ? !(e && e[0] == '0') : (e && e[0] == '1');
+}
+inline int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+// FSCNN_F32_SPLIT=0: the eval-form fp32 GEMMs on exact fp32 MFMA instead of three bf16 planes
+// (gemm.hip, gemm_stream.hip)
+inline bool f32_split_on() {
+  static const bool on = env_on("FSCNN_F32_SPLIT");
+  return on;
+}
 
 // ---- in-library launch profiler (bench.py roofline: HIP events on the launch stream) ---------
 enum ProfKind : int {

@@ -563,10 +563,9 @@ int gemm_nt(const GemmArgs& a, int dtype, hipStream_t st) {
     set_error("gemm_nt: empty problem M=%d N=%d K=%d", a.M, a.N, a.K);
     return E_INVALID;
   }
-  // C null: a statistics-only pass (the BN records of an output that is recomputed, not stored)
-  if (!a.C && !(a.part && !a.R && !a.bpart && gemm_stream_ok(a, dtype))) {
-    set_error("gemm_nt: no output (statistics only) needs the streaming kernel with statistics");
-    return E_UNSUPPORTED;
+  if (!a.C) {
+    set_error("gemm_nt: the output C is null (M=%d N=%d K=%d)", a.M, a.N, a.K);
+    return E_INVALID;
   }
   if (a.lda % V || (uintptr_t)a.A % 16 || (uintptr_t)a.B % 16 || a.ldb % V) {
     set_error("gemm_nt: operands must be 16-B aligned with ld multiple of %d (lda=%d ldb=%d)", V,
@@ -640,11 +639,9 @@ int gemm_nt(const GemmArgs& a, int dtype, hipStream_t st) {
 
 static int gemm_nt_tiled(const GemmArgs& a, int dtype, int nt, bool at, bool bs, hipStream_t st) {
   if (dtype == DT_F32) {
-    static const bool x3 = [] {  // FSCNN_F32_SPLIT=0: exact fp32 MFMA (gemm_stream.hip)
-      const char* e = getenv("FSCNN_F32_SPLIT");
-      return !(e && e[0] == '0');
-    }();
-    if (x3 && !a.b_trans && !bs && !at && !a.part) launch_nt<float, false, false, false, true>(a, nt, st);
+    // (the bf16-plane form; FSCNN_F32_SPLIT=0: exact fp32 MFMA)
+    if (f32_split_on() && !a.b_trans && !bs && !at && !a.part)
+      launch_nt<float, false, false, false, true>(a, nt, st);
     else if (a.b_trans) launch_nt<float, true, false>(a, nt, st);
     else if (bs) launch_nt<float, false, true>(a, nt, st);
     else if (at) launch_nt<float, false, false, true>(a, nt, st);

@@ -473,7 +473,7 @@ __global__ __launch_bounds__(256, 2) void gemm_stream_kernel(GemmArgs a, int bpg
               o[r] = dropout_keep(dseed, nchw, a.drop_thr) ? round_as<T>(o[r]) * dscale : 0.f;
             }
           }
-          if (mok && Cp) st4v(Cp + mr * a.ldc + n0 + nl, o);  // (C null: statistics only)
+          if (mok) st4v(Cp + mr * a.ldc + n0 + nl, o);
           if constexpr (BS) {  // partials of the value as stored, masked by that BN's ReLU
             const float4 bm = *reinterpret_cast<const float4*>(sbc + nl);
             const float4 bv = *reinterpret_cast<const float4*>(sbc + BN + nl);
@@ -505,7 +505,7 @@ __global__ __launch_bounds__(256, 2) void gemm_stream_kernel(GemmArgs a, int bpg
             if (n >= a.N) continue;
             float v = acc[mt][nt][r] * ssc[nl + r] + ssc[BN + nl + r];
             if (Rp) v += ld1(Rp + (size_t)m * a.ldr + n);
-            if (Cp) st1(Cp + (size_t)m * a.ldc + n, a.relu ? fmaxf(v, 0.f) : v);
+            st1(Cp + (size_t)m * a.ldc + n, a.relu ? fmaxf(v, 0.f) : v);
           }
         }
       }
@@ -729,25 +729,13 @@ __global__ __launch_bounds__(256, 2) void gemm_stream_x3_kernel(GemmArgs a, int 
   }
 }
 
-// eval-form fp32 GEMM on the bf16 matrix cores: FSCNN_F32_SPLIT=0 keeps exact fp32 MFMA
-static bool gs_x3_on() {
-  static const bool on = [] {
-    const char* e = getenv("FSCNN_F32_SPLIT");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
 // The largest column tile count of the statistics forms above N = 64: 4.  Their per-lane
 // shifted sums (8 NT registers) put the NT = 6 form at 256 VGPRs (2 waves per SIMD); measured
 // r06, cfg3 bf16, same box, two pairs: cap 4 5.777 / 5.771 ms per step, NT = 6 (the previous
 // choice for N % 96 == 0) 5.786 / 5.780, cap 3 5.841 / 5.808, cap 2 5.860 / 5.863.
 // FSCNN_GS_ST_NT overrides it (tuning A/B; 0: no cap).
 static int gs_st_nt_cap() {
-  static const int v = [] {
-    const char* e = getenv("FSCNN_GS_ST_NT");
-    return e ? atoi(e) : 4;
-  }();
+  static const int v = env_int("FSCNN_GS_ST_NT", 4);
   return v;
 }
 
@@ -927,9 +915,9 @@ static void gs_launch(const GemmArgs& a, int dtype, hipStream_t st) {
 }
 
 // fp32 eval GEMMs with K <= 128 on the bf16 matrix cores (gemm_stream_x3_kernel): the widest
-// column tile whose three weight planes fit 72 KB of LDS
+// column tile whose three weight planes fit 72 KB of LDS; FSCNN_F32_SPLIT=0 keeps exact fp32 MFMA
 static bool gs_x3_launch(const GemmArgs& a, hipStream_t st) {
-  if (!gs_x3_on() || a.part || a.bpart || a.a_scale || a.K > 128) return false;
+  if (!f32_split_on() || a.part || a.bpart || a.a_scale || a.K > 128) return false;
   const int ks = cdiv(a.K, 32);
   auto lds_of = [&](int nt) { return (size_t)3 * 16 * nt * (4 * ks + 1) * 16 + (size_t)2 * 16 * nt * 4; };
   int nt = gs_pick_nt(a, ks);

@@ -478,18 +478,9 @@ struct IrArgs {
   // ([3][E][Cin], [3][Cout][E]; weights_prep mode 3), or null (the kernel splits them)
   const uint16_t* we3 = nullptr;
   const uint16_t* wp3 = nullptr;
-  // training form (ir_train_fwd: expand recomputed + depthwise, no project): the input's lazily
-  // applied BN + ReLU (or null), sc_e / sh_e = BN_e's batch-statistics table, y = the depthwise's
-  // pre-BN output [N,H,W][ldy] and part = its BN records [tiles][3][E]
-  const float* x_scale = nullptr;
-  const float* x_shift = nullptr;
-  float* part = nullptr;
 };
 bool ir_block_ok(const IrArgs& a, int dtype);
 int ir_block_fwd(const IrArgs& a, int dtype, hipStream_t st);
-bool ir_train_ok(const IrArgs& a, int dtype);
-long long ir_train_parts(int N, int H, int W, int stride);
-int ir_train_fwd(const IrArgs& a, int dtype, hipStream_t st);
 
 // inference LearningToDownsample stem (stem.hip): conv0 + BN + ReLU -> dsconv1.dw + BN + ReLU ->
 // dsconv1.pw + BN + ReLU in one launch (models/fast_scnn.py:153-154), BatchNorms folded
@@ -642,8 +633,6 @@ int colsum(const void* D, int M, int N, int ld, float* part, int dtype, hipStrea
 
 int bn_fold(const FoldTable& t, hipStream_t st);
 int bn_finalize(const BnFinalizeArgs& a, hipStream_t st);
-// FSCNN_TAIL_INK bitmask of the producers that finish their BN in-kernel (A/B, bisection):
-// 1 tiled gemm_nt, 2 depthwise forward, 4 depthwise stride-1 dgrad, 8 stride-2 dgrad
 int bn_apply(const BnApplyArgs& a, int dtype, hipStream_t st);
 int bn_bwd_parts(long long M, int C, int dtype, int* rows_per_block);
 int bn_bwd_reduce(const BnBwdArgs& a, int dtype, hipStream_t st);

@@ -165,10 +165,7 @@ int dwout(int h, int s) { return (h - 1) / s + 1; }
 
 // FSCNN_IR_S2=0: the stride-2 bottlenecks (1.0, 2.0) as three unfused launches in inference
 static bool ir_stride2_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("FSCNN_IR_S2");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = env_on("FSCNN_IR_S2");
   return on;
 }
 // shape of bottleneck i as one fused inference launch (ir.hip); false when the block runs as
@@ -193,21 +190,6 @@ bool ir_block_shape(const Net& net, const Plan& pl, int i, IrArgs& b) {
   const int th = l.stride == 2 ? 4 : 8;
   const long long tiles = (long long)b.N * ((b.H + th - 1) / th) * ((b.W + 7) / 8);
   return ir_stride2_enabled() || l.stride == 1 ? tiles >= 128 && ir_block_ok(b, pl.dtype) : false;
-}
-
-// FSCNN_IR_TRAIN: training plans recompute the 6x-expanded tensor of these bottlenecks instead
-// of storing it (ir.hip ir_train_fwd + a statistics-only expand pass; the backward recomputes it):
-// 0 none (default), 1 bottleneck1 (the 201 / 50 / 50 MB tensors at cfg3), 2 every bottleneck.
-// Measured r06 (cfg3 bf16, same box, two pairs): 6.028 / 6.035 ms per step with bottleneck1
-// recomputed vs 5.815 / 5.815 stored -- the statistics-only expand costs 76 of the stored
-// expand's 103 us (its epilogue's statistics, not its stores, dominate), the fused tile kernel
-// 113 us against the depthwise's 91, and the backward's recompute another 137 us
-static int ir_train_blocks() {
-  static const int v = [] {
-    const char* e = getenv("FSCNN_IR_TRAIN");
-    return e ? atoi(e) : 0;
-  }();
-  return v;
 }
 
 int plan_build(const Net& net, int N, int H, int W, int dtype, int train, Plan& pl) {
@@ -272,9 +254,7 @@ int plan_build(const Net& net, int N, int H, int W, int dtype, int train, Plan& 
     int Ho = i < 3 ? pl.H4 : pl.H5, Wo = i < 3 ? pl.W4 : pl.W5;
     int e = l.cin * 6;
     unit(pl.lbe[i], Min, e, gemm_parts((int)Min));
-    // (the training form of ir.hip writes one BN_d record per output tile)
-    unit(pl.lbd[i], Mout, e, std::max<int>(dw_parts(N, Ho, Wo, e, dtype, l.stride),
-                                          (int)ir_train_parts(N, Ho, Wo, l.stride)));
+    unit(pl.lbd[i], Mout, e, dw_parts(N, Ho, Wo, e, dtype, l.stride));
     if (i == 8) unit(pl.lbp[i], Mout, l.cout, gemm_parts((int)Mout), pl.concat, 256);
     else unit(pl.lbp[i], Mout, l.cout, gemm_parts((int)Mout));
   }
@@ -581,10 +561,7 @@ struct SideStream {
     // the side stream at the lowest priority the device offers (FSCNN_SIDE_PRIO: 0 = plain
     // stream, 2 = the highest): measured r04 5.944-5.957 ms/step vs 5.984-5.985 (plain) and
     // 5.993-5.995 (highest) -- the main stream's latency-bound chain gets the CUs first
-    static const int prio_mode = [] {
-      const char* e = getenv("FSCNN_SIDE_PRIO");
-      return e ? atoi(e) : 1;
-    }();
+    static const int prio_mode = env_int("FSCNN_SIDE_PRIO", 1);
     // (a CU-masked side stream, hipExtStreamCreateWithCUMask on 1/2 or 1/4 of the CUs, measured
     // r04 10.6 / 12.3 ms per step: not an option)
     if (prio_mode) {
@@ -603,11 +580,9 @@ struct SideStream {
     // cfg3 step (same box; device-scope-release events 5.693 / 5.696); every side-stream path stays
     // bit-identical to one stream (test_switch_train_steps_bit_identical_with_dropout).
     // FSCNN_SIDE_FENCE=1 restores the default (fenced) events.
-    static const unsigned evf = [] {
-      const char* e = getenv("FSCNN_SIDE_FENCE");
-      return (unsigned)hipEventDisableTiming |
-             (e && e[0] == '1' ? 0u : (unsigned)hipEventDisableSystemFence);
-    }();
+    static const bool fenced = env_on("FSCNN_SIDE_FENCE", false);
+    const unsigned evf = (unsigned)hipEventDisableTiming |
+                         (fenced ? 0u : (unsigned)hipEventDisableSystemFence);
     hipEvent_t* ev[2] = {&fork, &join};
     for (auto* e : ev)
       if (hipEventCreateWithFlags(e, evf) != hipSuccess) return false;
@@ -653,20 +628,14 @@ bool graphs_enabled();
 // FSCNN_SIDE_STREAM=0: every weight gradient on the caller's stream (one stream; debugging and
 // A/B; tests/test_gpu_switches.py keeps it parity-green)
 bool side_stream_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("FSCNN_SIDE_STREAM");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = env_on("FSCNN_SIDE_STREAM");
   return on;
 }
 
 // FSCNN_LTD_FUSED=0: LTD.dsconv1.dw's input gradient stored and conv0's weight gradient as its
 // own launch (conv0_wgrad) instead of the fused ltd_c0_bwd (A/B; tests/test_gpu_switches.py)
 bool ltd_fused_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("FSCNN_LTD_FUSED");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = env_on("FSCNN_LTD_FUSED");
   return on;
 }
 
@@ -674,10 +643,7 @@ bool ltd_fused_enabled() {
 // BN-backward reduce as its own pass, instead of both in the classifier conv's dgrad epilogue
 // (A/B; tests/test_gpu_switches.py)
 bool drop_dgrad_on() {
-  static const bool on = [] {
-    const char* e = getenv("FSCNN_DROP_FUSED");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = env_on("FSCNN_DROP_FUSED");
   return on;
 }
 
@@ -992,53 +958,40 @@ struct Exec {
     return u.lazy ? OK : apply(u, true);
   }
 
+  // ---- inference-fusion switches (each =0 runs the unfused launches) ------------------------
   // inference stem fusion (stem.hip); FSCNN_STEM_FUSED=0 runs the three unfused launches (the
   // bit-identity test, tests/test_gpu_switches.py)
   static bool stem_enabled() {
-    static const bool on = [] {
-      const char* e = getenv("FSCNN_STEM_FUSED");
-      return !(e && e[0] == '0');
-    }();
+    static const bool on = env_on("FSCNN_STEM_FUSED");
     return on;
   }
   // inference LearningToDownsample.dsconv2 in one launch (dsconv.hip ds2_fwd);
   // FSCNN_LTD2_FUSED=0 runs its depthwise and pointwise launches (the bit-identity test,
   // tests/test_gpu_switches.py)
   static bool ltd2_enabled() {
-    static const bool on = [] {
-      const char* e = getenv("FSCNN_LTD2_FUSED");
-      return !(e && e[0] == '0');
-    }();
+    static const bool on = env_on("FSCNN_LTD2_FUSED");
     return on;
   }
   // inference PPM branch convs in one launch (ppm.hip); FSCNN_PPM_FUSED=0 runs the four pointwise
   // launches (the bit-identity test, tests/test_gpu_switches.py)
   static bool ppm_eval_enabled() {
-    static const bool on = [] {
-      const char* e = getenv("FSCNN_PPM_FUSED");
-      return !(e && e[0] == '0');
-    }();
+    static const bool on = env_on("FSCNN_PPM_FUSED");
     return on;
   }
   // inference DSConv fusion (dsconv.hip: the classifier's two DSConvs, the FFM's dwconv +
   // conv_lower_res); FSCNN_DSCONV_FUSED=0 runs dw + pw as two launches (the bit-identity test,
   // tests/test_gpu_switches.py)
   static bool ds_enabled() {
-    static const bool on = [] {
-      const char* e = getenv("FSCNN_DSCONV_FUSED");
-      return !(e && e[0] == '0');
-    }();
+    static const bool on = env_on("FSCNN_DSCONV_FUSED");
     return on;
   }
   // FSCNN_FFM_HI=0: the FFM's high-res branch runs as its own GEMM (the fused launch then adds its
   // stored output as a residual)
   static bool ffm_hi_enabled() {
-    static const bool on = [] {
-      const char* e = getenv("FSCNN_FFM_HI");
-      return !(e && e[0] == '0');
-    }();
+    static const bool on = env_on("FSCNN_FFM_HI");
     return on;
   }
+
   int fold_all() {
     FoldTable t{};
     auto add = [&](const BnL& bn, const Unit& u, const ConvL* conv) {
@@ -1168,14 +1121,8 @@ struct Exec {
         Hc = Ho; Wc = Wo;
         continue;
       }
-      IrArgs tb;
-      const In xin = i == 0 ? act(pl.l2pw) : raw(x, xld);
-      if (irt_shape(i, xin, tb)) {
-        TRY(irt_forward(i, xin, tb));
-      } else {
-        TRY(pw(pl.lbe[i], l.e, &l.be, xin, true));
-        TRY(dw(pl.lbd[i], l.d, l.bd, act(pl.lbe[i]), Hc, Wc, Ho, Wo, l.stride));
-      }
+      TRY(pw(pl.lbe[i], l.e, &l.be, i == 0 ? act(pl.l2pw) : raw(x, xld), true));
+      TRY(dw(pl.lbd[i], l.d, l.bd, act(pl.lbe[i]), Hc, Wc, Ho, Wo, l.stride));
       bool shortcut = l.stride == 1 && l.cin == l.cout;
       TRY(pw(pl.lbp[i], l.p, &l.bp, act(pl.lbd[i]), false, shortcut ? x : nullptr,
              shortcut ? xld : 0));
@@ -1396,68 +1343,6 @@ struct Exec {
     u.N = N; u.Hi = pl.H3; u.Wi = pl.W3; u.C = net.num_classes; u.Ho = pl.H; u.Wo = pl.W;
     u.x = W(pl.logits); u.ldx = pl.Cp; u.y = r.out; u.ldy = 0;
     return up_nchw(u, dt, r.out_dtype, r.st);
-  }
-
-  // ---- training bottleneck with the expanded tensor recomputed (ir.hip ir_train_fwd) ----------
-  // (models/fast_scnn.py:102-107) 16-bit training plans, the blocks ir_train_blocks() selects
-  bool irt_shape(int i, const In& xin, IrArgs& b) const {
-    const int sel = ir_train_blocks();
-    if (pl.train != 1 || frozen || dt == DT_F32 || sel == 0 || (sel == 1 && i >= 3)) return false;
-    const LbL& l = net.lb[i];
-    b = IrArgs{};
-    b.N = pl.N; b.stride = l.stride;
-    b.H = i < 3 ? pl.H4 : pl.H5; b.W = i < 3 ? pl.W4 : pl.W5;
-    b.Hi = i == 0 ? pl.H3 : (i < 4 ? pl.H4 : pl.H5);
-    b.Wi = i == 0 ? pl.W3 : (i < 4 ? pl.W4 : pl.W5);
-    b.Cin = l.cin; b.E = l.cin * 6; b.Cout = l.cout;
-    b.x = xin.p; b.ldx = xin.ld; b.x_scale = xin.sc; b.x_shift = xin.sh;
-    b.we = Wg(l.e); b.wd = P(l.d.w);
-    b.sc_e = Wf(pl.lbe[i].scale); b.sh_e = Wf(pl.lbe[i].shift);
-    b.y = W(pl.lbd[i].z); b.ldy = b.E; b.part = Wf(pl.lbd[i].part);
-    // the statistics-only pass needs the streaming GEMM (M >= 4096 pixels)
-    GemmArgs g = expand_args(i, xin);
-    g.part = Wf(pl.lbe[i].part);
-    return ir_train_parts(b.N, b.H, b.W, b.stride) <= pl.lbd[i].nparts && ir_train_ok(b, dt) &&
-           gemm_stream_ok(g, dt);
-  }
-  // the expand conv as a GEMM over the block input (statistics only, or the recompute)
-  GemmArgs expand_args(int i, const In& xin) const {
-    const LbL& l = net.lb[i];
-    const Unit& ue = pl.lbe[i];
-    GemmArgs g{};
-    g.M = (int)ue.M; g.N = ue.C; g.K = l.cin;
-    g.A = xin.p; g.lda = xin.ld; g.a_scale = xin.sc; g.a_shift = xin.sh;
-    g.B = Wg(l.e); g.ldb = l.cin;
-    g.shift = P(l.e.b);
-    g.ldc = ue.C;
-    return g;
-  }
-  int irt_forward(int i, const In& xin, IrArgs& b) {
-    const LbL& l = net.lb[i];
-    const Unit &ue = pl.lbe[i], &ud = pl.lbd[i];
-    // BN_e's batch statistics: the expand GEMM with no output (its records + in-kernel finish)
-    g_prof_tag = ue.name.c_str();
-    GemmArgs g = expand_args(i, xin);
-    g.C = nullptr;
-    gemm_fin(g, ue, l.be);
-    TRY(gemm_nt(g, dt, r.st));
-    // expand recomputed per tile -> BN_e + ReLU -> depthwise: only its pre-BN output stored
-    g_prof_tag = ud.name.c_str();
-    TRY(ir_train_fwd(b, dt, r.st));
-    BnFinalizeArgs f = fin_args(ud, l.bd);
-    f.P = (int)ir_train_parts(b.N, b.H, b.W, b.stride);
-    return bn_finalize(f, r.st);
-  }
-  // the backward's copy of the expand output the forward never stored: the same GEMM (same MFMA
-  // k order, rounded to the storage type) as the statistics pass, with its output
-  int irt_recompute(int i) {
-    const In xin = i == 0 ? act(pl.l2pw) : raw(W(pl.lbp[i - 1].a), pl.lbp[i - 1].ld);
-    IrArgs tb;
-    if (!irt_shape(i, xin, tb)) return OK;
-    g_prof_tag = pl.lbe[i].name.c_str();
-    GemmArgs g = expand_args(i, xin);
-    g.C = W(pl.lbe[i].z);
-    return gemm_nt(g, dt, r.st);
   }
 
   // FFM conv_higher_res (models/fast_scnn.py:202) + its BN statistics (train): on the side
@@ -1964,7 +1849,6 @@ struct Exec {
     int gxld = i == 0 ? 64 : pl.lbp[i - 1].ga_ld;
     bool shortcut = l.stride == 1 && l.cin == l.cout;
     const int e = l.cin * 6;
-    TRY(irt_recompute(i));  // (the expanded tensor, when the forward did not store it)
     // up's dy was produced by block i+1's expand dgrad with fused partials (not for the last
     // block: its dy is the PPM concat gradient)
     Dz d;
@@ -2098,10 +1982,7 @@ namespace {
 // slower than direct stream launches (9.46 vs 8.94 ms per cfg3 step) while the host enqueue
 // time (2.0 vs 3.6 ms) was never the bottleneck.
 bool graphs_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("FSCNN_GRAPHS");
-    return e && e[0] == '1';
-  }();
+  static const bool on = env_on("FSCNN_GRAPHS", false);
   return on;
 }
 

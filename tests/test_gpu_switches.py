@@ -1,5 +1,5 @@
-"""Every executor switch left in the library (`getenv` in fast-scnn-pytorch_amd/csrc) keeps its
-non-default path parity-green.  The switches are read once per process, so each case runs in a
+"""Every executor switch left in the library (`env_on` / `env_int`, the only `getenv` in
+fast-scnn-pytorch_amd/csrc) keeps its non-default path parity-green.  The switches are read once per process, so each case runs in a
 fresh child process:
 
 * ``FSCNN_SIDE_STREAM=0`` — every weight gradient on the caller's stream (one stream);
@@ -34,7 +34,8 @@ fresh child process:
   (test_ppm_fused_bit_identical).
 
 (Round 5 removed the measured-slower variants and their switches: FSCNN_DW_LOOP, FSCNN_GEMM_PF,
-FSCNN_CE_HEAD, FSCNN_CE_PACK, FSCNN_GEMM_MINT.)
+FSCNN_CE_HEAD, FSCNN_CE_PACK, FSCNN_GEMM_MINT; round 6's clean-up removed the training recompute
+of the bottleneck's expanded tensor and its switch, measured +0.21 ms per step.)
 
 Each child re-runs the oracle / golden parity tests that cover the path (fp32 train golden +
 bf16 emulated budget; eval goldens for the fp32 GEMM switch).  The graph switch also replays
@@ -69,9 +70,7 @@ CASES = {"FSCNN_SIDE_STREAM=0": TRAIN, "FSCNN_F32_SPLIT=0": EVAL,
          "FSCNN_SIDE_FENCE=1": TRAIN[:1],
          "FSCNN_DROP_FUSED=0": TRAIN[:1] + HEAD16, "FSCNN_STEM_FUSED=0": EVAL,
          "FSCNN_DSCONV_FUSED=0": EVAL, "FSCNN_IR_S2=0": EVAL, "FSCNN_FFM_HI=0": EVAL,
-         "FSCNN_PPM_FUSED=0": EVAL, "FSCNN_LTD2_FUSED=0": EVAL,
-         "FSCNN_IR_TRAIN=1": TRAIN[-1:] + ["tests/test_gpu_bf16_train.py"],
-         "FSCNN_IR_TRAIN=2": TRAIN[-1:] + ["tests/test_gpu_bf16_train.py"]}
+         "FSCNN_PPM_FUSED=0": EVAL, "FSCNN_LTD2_FUSED=0": EVAL}
 
 
 def _env(switch):
@@ -112,6 +111,17 @@ def _stem_worker(tmp_path, switch, dsconv=False, ppm=False):
     return dict(np.load(out))
 
 
+def _assert_outputs_bit_identical(ref, got):
+    """Every output of the two _stem_worker runs (all keys but the launch counter): finite and
+    bit-identical."""
+    for k in ref:
+        if k == "stem_launches":
+            continue
+        assert np.isfinite(got[k]).all(), k
+        assert np.array_equal(ref[k], got[k]), "%s: max |diff| %g" % (
+            k, float(np.abs(ref[k].astype(np.float64) - got[k]).max()))
+
+
 def test_stem_fused_bit_identical(tmp_path):
     """The fused inference stem (conv0 + LTD.dsconv1 dw + pw in one launch, csrc/stem.hip) gives
     bit-identical outputs to the three unfused launches: fp32 / bf16 / fp16 images, autocast fp16
@@ -120,12 +130,7 @@ def test_stem_fused_bit_identical(tmp_path):
     ref = _stem_worker(tmp_path, "FSCNN_STEM_FUSED=0")
     got = _stem_worker(tmp_path, None)
     assert int(ref["stem_launches"]) == 0 and int(got["stem_launches"]) == 1
-    for k in ref:
-        if k == "stem_launches":
-            continue
-        assert np.isfinite(got[k]).all(), k
-        assert np.array_equal(ref[k], got[k]), "%s: max |diff| %g" % (
-            k, float(np.abs(ref[k].astype(np.float64) - got[k]).max()))
+    _assert_outputs_bit_identical(ref, got)
 
 
 def test_dsconv_fused_bit_identical(tmp_path):
@@ -138,12 +143,7 @@ def test_dsconv_fused_bit_identical(tmp_path):
     got = _stem_worker(tmp_path, None, dsconv=True)
     # (+1 in both: LearningToDownsample.dsconv2's fused launch, FSCNN_LTD2_FUSED)
     assert int(ref["stem_launches"]) == 1 and int(got["stem_launches"]) == 4
-    for k in ref:
-        if k == "stem_launches":
-            continue
-        assert np.isfinite(got[k]).all(), k
-        assert np.array_equal(ref[k], got[k]), "%s: max |diff| %g" % (
-            k, float(np.abs(ref[k].astype(np.float64) - got[k]).max()))
+    _assert_outputs_bit_identical(ref, got)
 
 
 def test_ffm_hi_fused_bit_identical(tmp_path):
@@ -152,12 +152,7 @@ def test_ffm_hi_fused_bit_identical(tmp_path):
     ref = _stem_worker(tmp_path, "FSCNN_FFM_HI=0", dsconv=True)
     got = _stem_worker(tmp_path, None, dsconv=True)
     assert int(ref["stem_launches"]) == 4 and int(got["stem_launches"]) == 4
-    for k in ref:
-        if k == "stem_launches":
-            continue
-        assert np.isfinite(got[k]).all(), k
-        assert np.array_equal(ref[k], got[k]), "%s: max |diff| %g" % (
-            k, float(np.abs(ref[k].astype(np.float64) - got[k]).max()))
+    _assert_outputs_bit_identical(ref, got)
 
 
 def test_ltd2_fused_bit_identical(tmp_path):
@@ -170,12 +165,7 @@ def test_ltd2_fused_bit_identical(tmp_path):
     ref = _stem_worker(tmp_path, "FSCNN_LTD2_FUSED=0", dsconv=True)
     got = _stem_worker(tmp_path, None, dsconv=True)
     assert int(ref["stem_launches"]) == 3 and int(got["stem_launches"]) == 4
-    for k in ref:
-        if k == "stem_launches":
-            continue
-        assert np.isfinite(got[k]).all(), k
-        assert np.array_equal(ref[k], got[k]), "%s: max |diff| %g" % (
-            k, float(np.abs(ref[k].astype(np.float64) - got[k]).max()))
+    _assert_outputs_bit_identical(ref, got)
 
 
 def test_ppm_fused_bit_identical(tmp_path):
@@ -186,12 +176,7 @@ def test_ppm_fused_bit_identical(tmp_path):
     ref = _stem_worker(tmp_path, "FSCNN_PPM_FUSED=0", ppm=True)
     got = _stem_worker(tmp_path, None, ppm=True)
     assert int(ref["stem_launches"]) == 0 and int(got["stem_launches"]) == 1
-    for k in ref:
-        if k == "stem_launches":
-            continue
-        assert np.isfinite(got[k]).all(), k
-        assert np.array_equal(ref[k], got[k]), "%s: max |diff| %g" % (
-            k, float(np.abs(ref[k].astype(np.float64) - got[k]).max()))
+    _assert_outputs_bit_identical(ref, got)
 
 
 @pytest.mark.parametrize("switch", ["FSCNN_GRAPHS=1", "FSCNN_SIDE_STREAM=0", "FSCNN_SIDE_FENCE=1"])
@@ -295,51 +280,3 @@ def test_drop_fused_matches_separate_passes(tmp_path):
             floor = 1e-3 * float(np.abs(a).max())
             assert err <= (1e-3 if n in near else 1e-1) * scale + floor, (i, n, err, scale)
     print("drop fused vs separate: worst relative %.2e (%s)" % worst)
-
-
-def _irt_worker(tmp_path, switch):
-    out = str(tmp_path / ("irt_%s.npz" % (switch or "default").replace("=", "_")))
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "_irt_worker.py"), out],
-                       cwd=ROOT, env=_env(switch), capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
-    return dict(np.load(out))
-
-
-def test_ir_train_recompute_bit_identical(tmp_path):
-    """FSCNN_IR_TRAIN=1: the 16-bit training bottleneck1 blocks recompute the 6x-expanded tensor
-    (ir.hip ir_train_fwd after a statistics-only expand pass; the backward recomputes it for its
-    own use) instead of storing it -- opt-in, measured slower (net.cpp ir_train_blocks).
-    Against FSCNN_IR_TRAIN=0 (the default: expand stored, depthwise reads it):
-    the depthwise pre-BN outputs of the forward and the expand outputs the backward works from
-    are bit-identical, so only BN_d's statistics records are partitioned differently (per fused
-    tile instead of per depthwise workgroup: fp32 sums in another order).  Loss and gradients
-    then agree to that reordering, through bf16 storage; tests/test_gpu_bf16_train.py holds
-    both settings to the oracle (test_switch_keeps_oracle_parity)."""
-    a = _irt_worker(tmp_path, "FSCNN_IR_TRAIN=1")
-    b = _irt_worker(tmp_path, "FSCNN_IR_TRAIN=0")
-    for k in ("lbd0.z", "lbe0.z"):  # bottleneck1.0: identical inputs
-        assert np.array_equal(a[k], b[k]), (k, int((a[k] != b[k]).sum()))
-    np.testing.assert_allclose(a["lbd0.mean"], b["lbd0.mean"], rtol=1e-5, atol=1e-6)
-    # bottleneck1.1 / 1.2: their inputs went through BN_d of the block before (statistics
-    # reordered), so a few bf16 roundings of the inputs may differ: a one-ulp flip moves ~1 % of
-    # the next block's bf16 outputs by one ulp (measured r06: lbd2.z 0.66 % of elements, relative
-    # L2 3.4e-4; the element fraction was gated at 0.5 % until then, DESIGN.md §5)
-    for i in (1, 2):
-        for k in ("lbd%d.z" % i, "lbe%d.z" % i):
-            u = a[k].view(np.uint16).astype(np.uint32) << 16
-            v = b[k].view(np.uint16).astype(np.uint32) << 16
-            fu, fv = u.view(np.float32).astype(np.float64), v.view(np.float32).astype(np.float64)
-            frac = float((a[k] != b[k]).mean())
-            rel = np.linalg.norm(fu - fv) / np.linalg.norm(fv)
-            print("%s: %.4f%% elements differ, relative L2 %.2e" % (k, 100 * frac, rel))
-            assert frac < 2e-2 and rel < 1e-2, (k, frac, rel)
-    assert abs(float(a["loss"]) - float(b["loss"])) <= 1e-3 * abs(float(b["loss"]))
-    ga, gb = a["grad"].astype(np.float64), b["grad"].astype(np.float64)
-    cos = ga @ gb / (np.linalg.norm(ga) * np.linalg.norm(gb))
-    print("recompute vs stored: loss %.6f / %.6f, gradient cosine %.6f"
-          % (float(a["loss"]), float(b["loss"]), cos))
-    # (a BN_d record reordered at fp32 rounding moves bf16 roundings and ReLU masks downstream;
-    # at random init each flipped mask moves every upstream gradient, so two bf16 runs that
-    # differ only in summation order agree to cosine ~0.92 here -- the oracle parity of both
-    # settings is the gate, tests/test_gpu_bf16_train.py via test_switch_keeps_oracle_parity)
-    assert cos > 0.8, cos

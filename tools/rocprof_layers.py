@@ -45,7 +45,7 @@ FAMILY_RE = {
     "bn_bwd_reduce": r"bn_bwd_reduce_kernel",
     "bn_finalize": r"bn_(stats_fold_fin|stats_fold|finalize|bwd_fold_fin|bwd_fold|bwd_finalize)_kernel",
     "ppm_branches": r"ppm_(fwd|fwd_mma|eval_mma|bwd)_kernel",
-    "ir_block": r"ir_block_kernel|ir_train_fwd_kernel",
+    "ir_block": r"ir_block_kernel",
     "ltd_stem": r"stem_walk_kernel",
     "dsconv": r"dsconv_fwd_kernel|ds2_fwd_kernel",
 }
