@@ -11,12 +11,16 @@ Submodules:
   loss           fused cross-entropy criterion (HIP)
   optim          fused multi-tensor SGD and AdamW (HIP)
   ddp            one-process-per-GPU data parallel with bucketed RCCL gradient all-reduce
+  deploy         EndToEndFastSCNN — the deployment model: raw frames in, probabilities / mask out
 """
-__all__ = ["FastSCNN", "get_fast_scnn"]
+__all__ = ["FastSCNN", "get_fast_scnn", "EndToEndFastSCNN"]
 
 
 def __getattr__(name):
     if name in ("FastSCNN", "get_fast_scnn"):
         from . import fast_scnn
         return getattr(fast_scnn, name)
+    if name == "EndToEndFastSCNN":
+        from . import deploy
+        return deploy.EndToEndFastSCNN
     raise AttributeError(name)

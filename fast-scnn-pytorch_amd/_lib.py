@@ -11,11 +11,13 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FSCNN_LIB", os.path.join(_HERE, "libfastscnn_hip.so"))
 
 DT_F32, DT_BF16, DT_F16 = 0, 1, 2
+DT_U8 = 3  # frames of the deployment front end only (fscnn_e2e_pre)
 
 c_int, c_ll, c_float, c_vp, c_char_p = (ctypes.c_int, ctypes.c_longlong, ctypes.c_float,
                                         ctypes.c_void_p, ctypes.c_char_p)
 c_ull, c_double = ctypes.c_ulonglong, ctypes.c_double
 P_int, P_ll, P_vp = ctypes.POINTER(c_int), ctypes.POINTER(c_ll), ctypes.POINTER(c_vp)
+P_float = ctypes.POINTER(c_float)
 
 # name -> (restype, argtypes)
 SIGNATURES = {
@@ -60,6 +62,14 @@ SIGNATURES = {
     "fscnn_validate": (c_int, [c_vp, c_vp, c_int, c_vp, c_int, c_ll, c_float, c_float, c_float,
                                c_float, c_float, c_float, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                c_vp]),
+    "fscnn_e2e_pre": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P_float, P_float,
+                              c_vp, c_int, c_vp]),
+    "fscnn_e2e_head": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                               c_int, c_vp, c_int, c_vp, c_int, c_vp]),
+    "fscnn_e2e_ws_bytes": (c_ll, [c_vp]),
+    "fscnn_forward_e2e": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, P_float, P_float,
+                                  c_int, c_int, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp,
+                                  c_vp, c_vp]),
     "fscnn_seg_metric": (c_int, [c_vp, c_int, c_vp, c_ll, c_int, c_vp, c_vp]),
     "fscnn_forward_aux": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp,
                                   c_ull, c_float, c_float, c_vp]),

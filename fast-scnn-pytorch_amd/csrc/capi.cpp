@@ -434,6 +434,111 @@ int fscnn_validate(const fscnn_plan* plan, const void* x, int x_dtype, const lon
   GUARD(net_forward(plan->plan, r));
 }
 
+// ---- deployment pipeline (e2e.hip) -------------------------------------------------------------
+static int e2e_pre_args(const void* x, int channels_last, int bgr, int N, int h, int w, int base,
+                        const float* mean, const float* std, void* y, E2ePreArgs& a) {
+  if (!x || !y) {
+    set_error("fscnn_e2e_pre: null argument");
+    return E_INVALID;
+  }
+  if ((mean == nullptr) != (std == nullptr)) {
+    set_error("fscnn_e2e_pre: mean and std are given together or not at all");
+    return E_INVALID;
+  }
+  a.x = x; a.y = y; a.N = N; a.h = h; a.w = w; a.base = base; a.bgr = bgr != 0;
+  const long long hw = (long long)h * w;
+  a.sn = 3 * hw;
+  if (channels_last) { a.sc = 1; a.sy = 3LL * w; a.sx = 3; }
+  else { a.sc = hw; a.sy = w; a.sx = 1; }
+  for (int c = 0; c < 3; ++c) {
+    if (mean && !(std[c] != 0.f)) {
+      set_error("fscnn_e2e_pre: std[%d] is zero or NaN", c);
+      return E_INVALID;
+    }
+    const double s = mean ? (double)std[c] : 1.0;
+    a.A[c] = 1.0 / (255.0 * s);
+    a.B[c] = mean ? -(double)mean[c] / s : 0.0;
+  }
+  return OK;
+}
+
+int fscnn_e2e_pre(const void* x, int x_dtype, int channels_last, int bgr, int N, int h, int w,
+                  int base, const float* mean, const float* std, void* y, int y_dtype,
+                  void* stream) {
+  E2ePreArgs a{};
+  if (int rc = e2e_pre_args(x, channels_last, bgr, N, h, w, base, mean, std, y, a)) return rc;
+  return e2e_pre(a, x_dtype, y_dtype, S(stream));
+}
+
+int fscnn_e2e_head(const void* logits, int dtype, int N, int Hc, int Wc, int C, int ldx, int base,
+                   int h_out, int w_out, int softmax, void* probs, int probs_dtype,
+                   unsigned char* labels, int label_scale, void* stream) {
+  if (!logits) {
+    set_error("fscnn_e2e_head: null logits");
+    return E_INVALID;
+  }
+  E2eHeadArgs a{};
+  a.N = N; a.Hl = Hc; a.Wl = Wc; a.C = C; a.base = base; a.Ho = h_out; a.Wo = w_out;
+  a.logits = logits; a.ldx = ldx; a.softmax = softmax != 0; a.probs = probs;
+  a.probs_dtype = probs_dtype; a.labels = labels; a.label_scale = label_scale;
+  return e2e_head(a, dtype, S(stream));
+}
+
+static long long e2e_x_offset(const Plan& pl) {  // the front end's output, behind the forward ws
+  return ((long long)pl.ws_bytes + 255) / 256 * 256;
+}
+
+long long fscnn_e2e_ws_bytes(const fscnn_plan* plan) {
+  if (!plan || plan->plan.train) {
+    set_error("fscnn_e2e_ws_bytes: the deployment pipeline needs an inference plan (train=0)");
+    return E_INVALID;
+  }
+  const Plan& pl = plan->plan;
+  return e2e_x_offset(pl) + 3LL * pl.N * pl.H * pl.W * (pl.dtype == DT_F32 ? 4 : 2);
+}
+
+int fscnn_forward_e2e(const fscnn_plan* plan, const void* x, int x_dtype, int channels_last,
+                      int bgr, int h, int w, const float* mean, const float* std, int h_out,
+                      int w_out, int softmax, void* probs, int probs_dtype, unsigned char* labels,
+                      int label_scale, const float* params, float* running, long long* nbt,
+                      void* ws, void* stream) {
+  if (!plan || !x || !params || !running || !ws || (!probs && !labels)) {
+    set_error("fscnn_forward_e2e: null argument");
+    return E_INVALID;
+  }
+  const Plan& pl = plan->plan;
+  if (pl.train || pl.H != pl.W) {
+    set_error("fscnn_forward_e2e: needs an inference plan (train=0) of a square input, got "
+              "train=%d %dx%d", pl.train, pl.H, pl.W);
+    return E_INVALID;
+  }
+  if (probs && (probs_dtype < DT_F32 || probs_dtype > DT_F16)) {
+    set_error("fscnn_forward_e2e: probs dtype %d (0 fp32, 1 bf16, 2 fp16)", probs_dtype);
+    return E_INVALID;
+  }
+  // FSCNN_E2E_FUSED=0 (read on every call: tests compare the two routes in one process) reports
+  // every geometry as unsupported, which sends the caller down its unfused route
+  if (!env_on("FSCNN_E2E_FUSED")) {
+    set_error("fscnn_forward_e2e: switched off (FSCNN_E2E_FUSED=0)");
+    return E_UNSUPPORTED;
+  }
+  if (!e2e_head_ok(pl.N, pl.net->num_classes, pl.H3, pl.W3, pl.H, h_out, w_out)) {
+    set_error("fscnn_forward_e2e: the tail does not take this geometry (C=%d, %dx%d from base %d, "
+              "low-res %dx%d)", pl.net->num_classes, h_out, w_out, pl.H, pl.H3, pl.W3);
+    return E_UNSUPPORTED;
+  }
+  void* xin = (char*)ws + e2e_x_offset(pl);
+  E2ePreArgs a{};
+  if (int rc = e2e_pre_args(x, channels_last, bgr, pl.N, h, w, pl.H, mean, std, xin, a)) return rc;
+  if (int rc = e2e_pre(a, x_dtype, pl.dtype, S(stream))) return rc;
+  RunArgs r{};
+  r.x = xin; r.x_dtype = pl.dtype; r.out = nullptr; r.out_dtype = pl.dtype;
+  r.P = params; r.R = running; r.NBT = nbt; r.ws = ws; r.momentum = 0.1f; r.st = S(stream);
+  r.e2e_ho = h_out; r.e2e_wo = w_out; r.e2e_softmax = softmax != 0; r.e2e_probs = probs;
+  r.e2e_pdtype = probs_dtype; r.e2e_labels = labels; r.e2e_scale = label_scale;
+  GUARD(net_forward(plan->plan, r));
+}
+
 int fscnn_seg_metric(const void* pred, int pred_dtype, const long long* target, long long n,
                      int nclass, long long* counts, void* stream) {
   if ((!pred || !target || !counts) && n > 0) {

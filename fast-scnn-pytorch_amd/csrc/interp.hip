@@ -214,6 +214,13 @@ static int upr_max_rows(int Hi, int Ho, int UPR_R = fscnn::UPR_R) {
   return mx;
 }
 
+// whether up_nchw takes the row-group kernel for this geometry (e2e_head reproduces its stores)
+bool up_nchw_rows_path(const UpArgs& a) {
+  const int mr = upr_max_rows(a.Hi, a.Ho, UPR_RS);
+  return (size_t)mr * a.C * (a.Wi + 1) * sizeof(float) <= 64 * 1024 && a.N <= 65535 &&
+         mr <= UPR_MAXROWS;
+}
+
 int up_nchw(const UpArgs& a, int in_dtype, int out_dtype, hipStream_t st) {
   long long total = (long long)a.N * a.Ho * a.Wo;
   unsigned grid = (unsigned)((total + 255) / 256);
@@ -225,7 +232,7 @@ int up_nchw(const UpArgs& a, int in_dtype, int out_dtype, hipStream_t st) {
   // 255 with 2; 16 / 24 rows leave the chip underfilled, +350 us)
   constexpr int RR = UPR_RS;
   const size_t lds = (size_t)upr_max_rows(a.Hi, a.Ho, RR) * a.C * (a.Wi + 1) * sizeof(float);
-  if (lds <= 64 * 1024 && a.N <= 65535 && upr_max_rows(a.Hi, a.Ho, RR) <= UPR_MAXROWS) {
+  if (up_nchw_rows_path(a)) {
     dim3 g((unsigned)cdiv(a.Wo, UPR_COLS), (unsigned)cdiv(a.Ho, RR), (unsigned)a.N);
     const bool vec = a.Wo % 4 == 0;
     // staged rows per group (3 at cfg2's x8): the W-interpolations and selects of that many

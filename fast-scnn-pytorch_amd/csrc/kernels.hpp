@@ -646,6 +646,7 @@ int bn_bwd_apply(const BnBwdArgs& a, int dtype, hipStream_t st);
 int up_nhwc(const UpArgs& a, int dtype, hipStream_t st);
 int up_nchw(const UpArgs& a, int in_dtype, int out_dtype, hipStream_t st);
 // final upsample + argmax over classes -> labels [N][Ho][Wo] (int64, or uint8 when label_u8)
+bool up_nchw_rows_path(const UpArgs& a);
 int up_argmax(const UpArgs& a, int in_dtype, void* labels, int label_u8, hipStream_t st);
 // SegmentationMetric counters [2 + 3C] (int64, accumulated); see misc.hip
 int seg_metric(const void* pred, int pred_u8, const long long* target, long long n, int C,
@@ -704,6 +705,28 @@ int dice_head_scale(const void* head_ws, void* g, long long M, int C, int ld, co
 int eval_head_parts(int N, int H, int W);
 bool eval_head_ok(int N, int C, int Hl, int Wl, int H, int W, int dice);
 int eval_head(const EvalHeadArgs& a, int dtype, hipStream_t st);
+// Deployment pipeline (e2e.hip): the frame front end and the tail over the low-res logits, both
+// resampling with align_corners=False.  DT_U8: a frame dtype of e2e_pre only.
+constexpr int DT_U8 = 3;
+constexpr int E2E_MAXDIM = 16384;  // every size: the exact tap numerators stay below 2^30
+struct E2ePreArgs {
+  const void* x;             // frames, element strides below
+  long long sn, sc, sy, sx;  // NCHW: (3hw, hw, w, 1); NHWC: (3hw, 1, 3w, 3)
+  int N, h, w, base, bgr;
+  double A[3], B[3];         // y = lerp * A[c] + B[c]: 1 / (255 std), -mean / std
+  void* y;                   // NCHW [N][3][base][base]
+};
+int e2e_pre(const E2ePreArgs& a, int x_dtype, int y_dtype, hipStream_t st);
+struct E2eHeadArgs {
+  int N, Hl, Wl, C, base, Ho, Wo;
+  const void* logits; int ldx;  // NHWC [N][Hl][Wl][ldx]
+  int softmax;
+  void* probs; int probs_dtype;  // NCHW [N][C][Ho][Wo] or null
+  uint8_t* labels; int label_scale;  // [N][Ho][Wo] or null
+  int f16_once = 0;  // (set by e2e_head) fp16 taps: every column rounds once (e2e.hip tap_as_stored)
+};
+bool e2e_head_ok(int N, int C, int Hl, int Wl, int base, int Ho, int Wo);
+int e2e_head(const E2eHeadArgs& a, int dtype, hipStream_t st);
 int dropout(const DropArgs& a, int dtype, hipStream_t st);
 // GPU input path: ToTensor + Normalize of uint8 HWC images into NCHW (fp32 / bf16)
 int normalize_u8(const uint8_t* x, int N, int H, int W, const float* mean, const float* std,

@@ -1308,6 +1308,20 @@ struct Exec {
       }
       return OK;
     }
+    if (r.e2e_ho > 0) {
+      // ---- deployment tail: resample to the frame size + softmax / argmax, from the low-res logits
+      if (train || pl.H != pl.W) {
+        set_error("forward_e2e needs an inference plan (train=0) of a square input");
+        return E_INVALID;
+      }
+      g_prof_tag = "head (e2e resample + softmax)";
+      E2eHeadArgs h{};
+      h.N = N; h.Hl = pl.H3; h.Wl = pl.W3; h.C = net.num_classes; h.base = pl.H;
+      h.Ho = r.e2e_ho; h.Wo = r.e2e_wo; h.logits = W(pl.logits); h.ldx = pl.Cp;
+      h.softmax = r.e2e_softmax; h.probs = r.e2e_probs; h.probs_dtype = r.e2e_pdtype;
+      h.labels = r.e2e_labels; h.label_scale = r.e2e_scale;
+      return e2e_head(h, dt, r.st);
+    }
     if (r.target) {
       // ---- fused training head: upsample + CE + gradient at low resolution ----
       if (!train || frozen) {
@@ -2000,7 +2014,9 @@ std::vector<uint64_t> run_key(int kind, int s0, int s1, const RunArgs& r) {
           (uint64_t)r.ignore_index, P(r.loss2), P(r.gloss), P(r.dx), (uint64_t)r.dx_dtype,
           (uint64_t)r.head, fbits(r.smooth), fbits(r.dice_weight), fbits(r.focal_weight),
           fbits(r.alpha), fbits(r.gamma), P(r.head_ws), P(r.dice_stats), (uint64_t)r.validate,
-          fbits(r.aux_weight), P(r.counts)};
+          fbits(r.aux_weight), P(r.counts), (uint64_t)r.e2e_ho, (uint64_t)r.e2e_wo,
+          (uint64_t)r.e2e_softmax, (uint64_t)r.e2e_pdtype, (uint64_t)r.e2e_scale, P(r.e2e_probs),
+          P(r.e2e_labels)};
 }
 
 template <typename F>
@@ -2089,7 +2105,7 @@ int net_forward_impl(const Plan& pl, const RunArgs& r) {
     set_error("forward_loss: the fused loss head covers the main output only (aux net)");
     return E_UNSUPPORTED;
   }
-  if (pl.net->aux && !r.aux_out && !r.labels && !r.validate) {
+  if (pl.net->aux && !r.aux_out && !r.labels && !r.validate && r.e2e_ho <= 0) {
     set_error("fscnn_forward: this net has the aux head; use fscnn_forward_aux");
     return E_INVALID;
   }

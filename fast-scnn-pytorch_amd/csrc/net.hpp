@@ -182,6 +182,13 @@ struct RunArgs {
   int validate = 0;
   float aux_weight = 0.f;
   unsigned long long* counts = nullptr;
+  // deployment tail (inference plans, square input): forward with e2e_ho > 0 ends in e2e_head
+  // (e2e.hip) instead of the upsample: the logits resampled (align_corners=False) to
+  // e2e_ho x e2e_wo, as probabilities / logits into e2e_probs and / or scaled labels into
+  // e2e_labels
+  int e2e_ho = 0, e2e_wo = 0, e2e_softmax = 0, e2e_pdtype = 0, e2e_scale = 1;
+  void* e2e_probs = nullptr;
+  unsigned char* e2e_labels = nullptr;
   // backward: gradient of the input image, NCHW [N][3][H][W] in dx_dtype (autograd of x through
   // conv0, models/fast_scnn.py:153), or null
   void* dx = nullptr;

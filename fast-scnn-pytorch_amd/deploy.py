@@ -1,0 +1,213 @@
+"""The deployment model: raw camera frames in, class probabilities (or the lane mask) out.
+
+Drop-in for ``EndToEndFastSCNN`` of the reference's ``export_onnx_fixed.py:34-98``, the model that
+is exported for the car and that ``kuruma/core/inference.py``, ``onnx_single_image_inference.py``
+and ``lane_dashboard_e2e.py`` run:
+
+* resize the 0..255 frame to ``base_size x base_size`` (bilinear, ``align_corners=False``),
+  ``/ 255`` and optionally ``(x - mean) / std``            (``EndToEndPreprocessing``, :62-98);
+* the backbone;
+* resize the full-resolution logits back to ``input_size`` (bilinear, ``align_corners=False``) and
+  softmax over the classes (:53-58); the host then takes ``argmax * 255`` as the lane mask
+  (``kuruma/core/preprocessing.py:53-79``) -- here ``predict(frames, scale=255)``.
+
+Same constructor arguments in the same order, same sub-module names (``backbone``,
+``preprocessor`` with ``mean`` / ``std`` buffers only when both are given), hence the same
+``state_dict()`` keys.  The call is two launches around the backbone's inference plan
+(``csrc/e2e.hip``): the front end writes the backbone's input straight from the frame, and the
+tail reads the 1/8-resolution logits and writes only the ``input_size`` output -- neither the
+full-resolution logits nor, for ``predict``, any probability is ever formed.
+"""
+import ctypes
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _lib
+from .fast_scnn import E_UNSUPPORTED
+
+__all__ = ["EndToEndFastSCNN", "EndToEndPreprocessing"]
+
+_FRAME_DTYPES = {torch.uint8: _lib.DT_U8, torch.float32: _lib.DT_F32, torch.float16: _lib.DT_F16,
+                 torch.bfloat16: _lib.DT_BF16}
+
+
+class EndToEndPreprocessing(nn.Module):
+    """export_onnx_fixed.py:62-98: holds the normalisation constants; the arithmetic runs in the
+    wrapper's front-end kernel."""
+
+    def __init__(self, input_size=(640, 360), base_size=1024, mean=None, std=None):
+        super().__init__()
+        self.input_size = input_size
+        self.base_size = base_size
+        if mean is not None and std is not None:
+            self.register_buffer("mean", torch.tensor(mean).view(1, 3, 1, 1))
+            self.register_buffer("std", torch.tensor(std).view(1, 3, 1, 1))
+        else:
+            self.mean = None
+            self.std = None
+
+    def forward(self, *args, **kwargs):  # pragma: no cover - guard
+        raise RuntimeError("EndToEndPreprocessing is a buffer container; call the "
+                           "EndToEndFastSCNN module")
+
+
+class EndToEndFastSCNN(nn.Module):
+    """``EndToEndFastSCNN(backbone_model, input_size=(W, H), base_size, mean, std, apply_softmax)``
+    of the reference, plus three trailing keywords:
+
+    ``dtype``          arithmetic of the backbone and dtype of the output: fp32, fp16 (the Atlas
+                       deployment's) or bf16; an active ``torch.autocast("cuda")`` overrides it
+    ``channels_last``  frames are ``[N, h, w, 3]`` (a camera / OpenCV frame) instead of
+                       ``[N, 3, h, w]``
+    ``bgr``            frames carry their channels as B, G, R
+
+    Frames hold 0..255 values as uint8, fp32, fp16 or bf16; any ``h, w >= 2`` is taken, and the
+    output size is always ``input_size``, as in the reference.  The backbone must be in eval mode
+    and everything on a ROCm device.  ``_last_fused`` tells whether the last call ran the fused
+    tail or the unfused route (geometries the tail does not take, ``FSCNN_E2E_FUSED=0``)."""
+
+    def __init__(self, backbone_model, input_size=(640, 360), base_size=1024, mean=None, std=None,
+                 apply_softmax=True, dtype=torch.float32, channels_last=False, bgr=False):
+        super().__init__()
+        if base_size < 32:
+            raise RuntimeError("EndToEndFastSCNN: base_size %d too small (the backbone needs "
+                               ">= 32)" % base_size)
+        if dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            raise RuntimeError("EndToEndFastSCNN: dtype %s (fp32 / fp16 / bf16)" % (dtype,))
+        if len(input_size) != 2 or min(input_size) < 1:
+            raise RuntimeError("EndToEndFastSCNN: input_size is (W, H), got %s" % (input_size,))
+        self.backbone = backbone_model
+        self.preprocessor = EndToEndPreprocessing(input_size, base_size, mean, std)
+        self.apply_softmax = apply_softmax
+        self.input_size = input_size  # (W, H) of the output
+        self.base_size = base_size
+        self.dtype = dtype
+        self.channels_last = channels_last
+        self.bgr = bgr
+        object.__setattr__(self, "_last_fused", None)
+        object.__setattr__(self, "_norm", None)  # (key, host mean[3], host std[3])
+
+    # ---- pieces ---------------------------------------------------------------------------------
+    def _compute_dtype(self):
+        if torch.is_autocast_enabled("cuda"):
+            dt = torch.get_autocast_dtype("cuda")
+            if dt in (torch.float16, torch.bfloat16):
+                return dt
+            raise RuntimeError("EndToEndFastSCNN: unsupported autocast dtype %s" % (dt,))
+        return self.dtype
+
+    def _norm_host(self):
+        """The mean / std buffers as host float[3] arrays (what the library takes), refreshed when
+        the buffers were written (load_state_dict) or moved."""
+        m, s = self.preprocessor.mean, self.preprocessor.std
+        if m is None or s is None:
+            return None, None
+        key = (m.data_ptr(), m._version, s.data_ptr(), s._version)
+        if self._norm is None or self._norm[0] != key:
+            hm = (ctypes.c_float * 3)(*[float(v) for v in m.detach().float().reshape(3).cpu()])
+            hs = (ctypes.c_float * 3)(*[float(v) for v in s.detach().float().reshape(3).cpu()])
+            object.__setattr__(self, "_norm", (key, hm, hs))
+        return self._norm[1], self._norm[2]
+
+    def _check(self, frames):
+        if self.backbone.training:
+            raise RuntimeError("EndToEndFastSCNN is the inference pipeline; call model.eval() first")
+        if not isinstance(frames, torch.Tensor) or frames.dim() != 4:
+            raise RuntimeError("EndToEndFastSCNN: expected 4-d frames")
+        if not frames.is_cuda:
+            raise RuntimeError("EndToEndFastSCNN: the HIP path needs a ROCm device tensor (got %s); "
+                               "move the model and the frames to 'cuda'" % (frames.device,))
+        if frames.dtype not in _FRAME_DTYPES:
+            raise RuntimeError("EndToEndFastSCNN: frames are uint8 / fp32 / fp16 / bf16, not %s"
+                               % (frames.dtype,))
+        cdim = 3 if self.channels_last else 1
+        if frames.shape[cdim] != 3:
+            raise RuntimeError("EndToEndFastSCNN: expected frames %s, got %s"
+                               % ("[N, h, w, 3]" if self.channels_last else "[N, 3, h, w]",
+                                  tuple(frames.shape)))
+        N = frames.shape[0]
+        h, w = (frames.shape[1:3] if self.channels_last else frames.shape[2:4])
+        if N < 1 or h < 2 or w < 2:
+            raise RuntimeError("EndToEndFastSCNN: frames %s need N >= 1 and h, w >= 2"
+                               % (tuple(frames.shape),))
+        return frames.contiguous(), int(N), int(h), int(w)
+
+    def preprocess(self, frames, dtype=None):
+        """The front end alone: the backbone's input ``[N, 3, base, base]`` in ``dtype``."""
+        frames, N, h, w = self._check(frames)
+        dt = self._compute_dtype() if dtype is None else dtype
+        return self._pre(frames, N, h, w, dt)
+
+    def _pre(self, frames, N, h, w, dt):
+        base = self.base_size
+        x = torch.empty((N, 3, base, base), dtype=dt, device=frames.device)
+        hm, hs = self._norm_host()
+        with torch.cuda.device(frames.device):
+            _lib.call("fscnn_e2e_pre", _lib.ptr(frames), _FRAME_DTYPES[frames.dtype],
+                      int(self.channels_last), int(self.bgr), N, h, w, base, hm, hs, _lib.ptr(x),
+                      _lib.dtype_code(dt), _lib.stream_ptr(frames.device))
+        return x
+
+    def _run(self, frames, probs, scale):
+        """One pipeline call: probabilities / logits (``probs``) or the scaled labels."""
+        frames, N, h, w = self._check(frames)
+        bb, dev = self.backbone, frames.device
+        dt = self._compute_dtype()
+        wo, ho = int(self.input_size[0]), int(self.input_size[1])
+        base, C = self.base_size, bb.num_classes
+        with torch.no_grad():
+            nat = bb.native()
+            ar = bb._exec_arena(dev)
+            if ar["P"].device != dev:
+                raise RuntimeError("EndToEndFastSCNN: frames on %s but parameters on %s"
+                                   % (dev, ar["P"].device))
+            plan, _, _ = nat.plan(N, base, base, _lib.dtype_code(dt), False, dev)
+            lib = _lib.load()
+            need = int(lib.fscnn_e2e_ws_bytes(plan))
+            if need < 0:
+                _lib.check(need, "fscnn_e2e_ws_bytes")
+            ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+            out = torch.empty((N, C, ho, wo), dtype=dt, device=dev) if probs else None
+            labels = None if probs else torch.empty((N, ho, wo), dtype=torch.uint8, device=dev)
+            hm, hs = self._norm_host()
+            with torch.cuda.device(dev):
+                rc = lib.fscnn_forward_e2e(
+                    plan, _lib.ptr(frames), _FRAME_DTYPES[frames.dtype], int(self.channels_last),
+                    int(self.bgr), h, w, hm, hs, ho, wo, int(bool(self.apply_softmax)),
+                    _lib.ptr(out), _lib.dtype_code(dt), _lib.ptr(labels), int(scale) & 255,
+                    _lib.ptr(ar["P"]), _lib.ptr(ar["R"]), _lib.ptr(ar["NBT"]), _lib.ptr(ws),
+                    _lib.stream_ptr(dev))
+            fused = rc != E_UNSUPPORTED  # nothing was launched: the geometry check comes first
+            if fused:
+                _lib.check(rc, "fscnn_forward_e2e")
+            else:
+                out, labels = self._unfused(frames, N, h, w, dt, probs, scale)
+        object.__setattr__(self, "_last_fused", fused)
+        return out if probs else labels
+
+    def _unfused(self, frames, N, h, w, dt, probs, scale):
+        """The same results from full-resolution logits: the front-end kernel, ``backbone(x)[0]``
+        and torch's resize plus softmax or argmax (export_onnx_fixed.py:47-58)."""
+        wo, ho = int(self.input_size[0]), int(self.input_size[1])
+        x = self._pre(frames, N, h, w, dt)
+        y = self.backbone._run_forward(x, 0, dt=dt)[0][0]
+        if y.shape[2] != ho or y.shape[3] != wo:
+            y = F.interpolate(y, size=(ho, wo), mode="bilinear", align_corners=False)
+        if probs:
+            return (F.softmax(y, dim=1) if self.apply_softmax else y), None
+        return None, (torch.argmax(y, 1) * (int(scale) & 255)).to(torch.uint8)
+
+    # ---- the reference interface -----------------------------------------------------------------
+    def forward(self, frames):
+        """``[N, C, H, W]`` with ``(W, H) = input_size``: probabilities, or the resampled logits
+        when ``apply_softmax`` is false."""
+        return self._run(frames, True, 1)
+
+    def predict(self, frames, scale=1):
+        """uint8 ``[N, H, W]`` = ``(argmax over classes * scale)`` as uint8, wrapping the way
+        numpy's ``astype(uint8)`` does; ``scale=255`` is the deployment's lane mask
+        (kuruma/core/preprocessing.py:53-79).  Ties resolve to the lowest class, like
+        ``torch.argmax``.  No probability tensor is written."""
+        return self._run(frames, False, scale)

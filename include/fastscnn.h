@@ -139,6 +139,46 @@ int fscnn_validate(const fscnn_plan* plan, const void* x, int x_dtype, const lon
                    float focal_weight, float alpha, float gamma, float aux_weight, float* loss,
                    long long* counts, const float* params, float* running, long long* nbt,
                    void* ws, void* head_ws, void* stream);
+/* Deployment pipeline (EndToEndFastSCNN, export_onnx_fixed.py:34-98; the host's argmax * 255 lane
+ * mask, kuruma/core/preprocessing.py:53-79): raw 0..255 frames in, class probabilities out.
+ * Every resampling here is F.interpolate(mode='bilinear', align_corners=False) without
+ * antialiasing: output position o of an in -> out resize reads source position
+ * max((o + 0.5) * in / out - 0.5, 0), taps floor(s) and min(floor(s) + 1, in - 1); the position
+ * is evaluated exactly, as the rational ((2o + 1) in - out) / (2 out).  Every size is <= 16384.
+ *
+ * fscnn_e2e_pre: frames -> the backbone's input y, dense NCHW [N][3][base][base] in y_dtype
+ *   (0 fp32, 1 bf16, 2 fp16): resize h x w -> base x base, / 255, then (v - mean[c]) / std[c]
+ *   when both are given; fp32 lerp, one rounding at the store.  x: x_dtype 0 / 1 / 2 or
+ *   FSCNN_DT_U8 (3); NCHW [N][3][h][w], or NHWC [N][h][w][3] with channels_last != 0; bgr != 0
+ *   reads channel 2 - c for output channel c.  mean / std: HOST arrays of 3 floats (as
+ *   fscnn_normalize_u8), both or neither null.  h, w >= 2; base >= 1.
+ * fscnn_e2e_head: the low-resolution logits of an inference plan (NHWC [N][Hc][Wc][ldx], the
+ *   buffer fscnn_predict's head reads) -> the pipeline's output at h_out x w_out.  For each
+ *   output pixel the four taps of the base x base grid are formed exactly as fscnn_forward stores
+ *   them (align_corners=True upsample, rounded to the logits dtype), combined in fp32, and then
+ *   probs [N][C][h_out][w_out] in probs_dtype = their softmax over C (softmax != 0) or the
+ *   resampled logits themselves; labels [N][h_out][w_out] uint8 = (argmax * label_scale) mod 256,
+ *   ties to the lowest class.  Either output may be null.  Returns -2 (nothing launched) when
+ *   C > 32 or the low-resolution window of an output tile does not fit the LDS staging.
+ * fscnn_forward_e2e: front end, backbone and tail on `stream`; plan: an inference plan
+ *   (train = 0) created for N x base x base, whose dtype is the backbone's arithmetic and the
+ *   dtype of the front end's output.  ws: fscnn_e2e_ws_bytes(plan) bytes (negative for a training
+ *   plan) = the plan's forward workspace followed by the front end's output; nothing else of full
+ *   resolution is written.  Returns -2 before any launch where fscnn_e2e_head would. */
+#define FSCNN_DT_U8 3
+int fscnn_e2e_pre(const void* x, int x_dtype, int channels_last, int bgr, int N, int h, int w,
+                  int base, const float* mean, const float* std, void* y, int y_dtype,
+                  void* stream);
+int fscnn_e2e_head(const void* logits, int dtype, int N, int Hc, int Wc, int C, int ldx, int base,
+                   int h_out, int w_out, int softmax, void* probs, int probs_dtype,
+                   unsigned char* labels, int label_scale, void* stream);
+long long fscnn_e2e_ws_bytes(const fscnn_plan* plan);
+int fscnn_forward_e2e(const fscnn_plan* plan, const void* x, int x_dtype, int channels_last,
+                      int bgr, int h, int w, const float* mean, const float* std, int h_out,
+                      int w_out, int softmax, void* probs, int probs_dtype, unsigned char* labels,
+                      int label_scale, const float* params, float* running, long long* nbt,
+                      void* ws, void* stream);
+
 /* SegmentationMetric counters (utils/metric.py:73-105, batch_pix_accuracy +
  * batch_intersection_union) of n predictions (pred_dtype 0 int64, 1 uint8) against int64 labels,
  * ACCUMULATED into counts[2 + 3*nclass] (int64): [correct, labeled, inter[C], area_pred[C],
