@@ -12,8 +12,10 @@ Submodules:
   optim          fused multi-tensor SGD and AdamW (HIP)
   ddp            one-process-per-GPU data parallel with bucketed RCCL gradient all-reduce
   deploy         EndToEndFastSCNN — the deployment model: raw frames in, probabilities / mask out
+  bev            BirdEyeView / centerline — calibration, view parameters and the centreline read
+                 from the row table of EndToEndFastSCNN.bird_eye
 """
-__all__ = ["FastSCNN", "get_fast_scnn", "EndToEndFastSCNN"]
+__all__ = ["FastSCNN", "get_fast_scnn", "EndToEndFastSCNN", "BirdEyeView", "centerline"]
 
 
 def __getattr__(name):
@@ -23,4 +25,7 @@ def __getattr__(name):
     if name == "EndToEndFastSCNN":
         from . import deploy
         return deploy.EndToEndFastSCNN
+    if name in ("BirdEyeView", "centerline"):
+        from . import bev
+        return getattr(bev, name)
     raise AttributeError(name)

@@ -18,6 +18,7 @@ c_int, c_ll, c_float, c_vp, c_char_p = (ctypes.c_int, ctypes.c_longlong, ctypes.
 c_ull, c_double = ctypes.c_ulonglong, ctypes.c_double
 P_int, P_ll, P_vp = ctypes.POINTER(c_int), ctypes.POINTER(c_ll), ctypes.POINTER(c_vp)
 P_float = ctypes.POINTER(c_float)
+P_double = ctypes.POINTER(c_double)
 
 # name -> (restype, argtypes)
 SIGNATURES = {
@@ -70,6 +71,13 @@ SIGNATURES = {
     "fscnn_forward_e2e": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, P_float, P_float,
                                   c_int, c_int, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp,
                                   c_vp, c_vp]),
+    "fscnn_bev_mask": (c_int, [c_vp, c_int, c_int, c_int, P_double, c_int, c_int, c_int, c_vp, c_vp,
+                               c_vp]),
+    "fscnn_e2e_bev": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                              c_int, P_double, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
+    "fscnn_forward_e2e_bev": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, P_float,
+                                      P_float, c_int, c_int, c_int, P_double, c_int, c_int, c_int,
+                                      c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "fscnn_seg_metric": (c_int, [c_vp, c_int, c_vp, c_ll, c_int, c_vp, c_vp]),
     "fscnn_forward_aux": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp,
                                   c_ull, c_float, c_float, c_vp]),

@@ -1,6 +1,7 @@
 // extern "C" boundary of libfastscnn_hip.so (declared in include/fastscnn.h).
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdlib>
 #include <cstdarg>
 #include <cstdio>
@@ -497,6 +498,37 @@ long long fscnn_e2e_ws_bytes(const fscnn_plan* plan) {
   return e2e_x_offset(pl) + 3LL * pl.N * pl.H * pl.W * (pl.dtype == DT_F32 ? 4 : 2);
 }
 
+// fscnn_forward_e2e and fscnn_forward_e2e_bev: the front end, then the backbone ending in the tail
+// that `r` names.  tail_ok: the tail's geometry check, made before anything is launched.
+static int forward_e2e_run(const char* who, const fscnn_plan* plan, const void* x, int x_dtype,
+                           int channels_last, int bgr, int h, int w, const float* mean,
+                           const float* std, bool tail_ok, RunArgs& r, void* ws, void* stream) {
+  const Plan& pl = plan->plan;
+  if (pl.train || pl.H != pl.W) {
+    set_error("%s: needs an inference plan (train=0) of a square input, got train=%d %dx%d", who,
+              pl.train, pl.H, pl.W);
+    return E_INVALID;
+  }
+  // FSCNN_E2E_FUSED=0 (read on every call: tests compare the two routes in one process) reports
+  // every geometry as unsupported, which sends the caller down its unfused route
+  if (!env_on("FSCNN_E2E_FUSED")) {
+    set_error("%s: switched off (FSCNN_E2E_FUSED=0)", who);
+    return E_UNSUPPORTED;
+  }
+  if (!tail_ok) {
+    set_error("%s: the tail does not take this geometry (C=%d, %dx%d from base %d, low-res %dx%d)",
+              who, pl.net->num_classes, r.e2e_ho, r.e2e_wo, pl.H, pl.H3, pl.W3);
+    return E_UNSUPPORTED;
+  }
+  void* xin = (char*)ws + e2e_x_offset(pl);
+  E2ePreArgs a{};
+  if (int rc = e2e_pre_args(x, channels_last, bgr, pl.N, h, w, pl.H, mean, std, xin, a)) return rc;
+  if (int rc = e2e_pre(a, x_dtype, pl.dtype, S(stream))) return rc;
+  r.x = xin; r.x_dtype = pl.dtype; r.out = nullptr; r.out_dtype = pl.dtype;
+  r.ws = ws; r.momentum = 0.1f; r.st = S(stream);
+  GUARD(net_forward(plan->plan, r));
+}
+
 int fscnn_forward_e2e(const fscnn_plan* plan, const void* x, int x_dtype, int channels_last,
                       int bgr, int h, int w, const float* mean, const float* std, int h_out,
                       int w_out, int softmax, void* probs, int probs_dtype, unsigned char* labels,
@@ -506,37 +538,77 @@ int fscnn_forward_e2e(const fscnn_plan* plan, const void* x, int x_dtype, int ch
     set_error("fscnn_forward_e2e: null argument");
     return E_INVALID;
   }
-  const Plan& pl = plan->plan;
-  if (pl.train || pl.H != pl.W) {
-    set_error("fscnn_forward_e2e: needs an inference plan (train=0) of a square input, got "
-              "train=%d %dx%d", pl.train, pl.H, pl.W);
-    return E_INVALID;
-  }
   if (probs && (probs_dtype < DT_F32 || probs_dtype > DT_F16)) {
     set_error("fscnn_forward_e2e: probs dtype %d (0 fp32, 1 bf16, 2 fp16)", probs_dtype);
     return E_INVALID;
   }
-  // FSCNN_E2E_FUSED=0 (read on every call: tests compare the two routes in one process) reports
-  // every geometry as unsupported, which sends the caller down its unfused route
-  if (!env_on("FSCNN_E2E_FUSED")) {
-    set_error("fscnn_forward_e2e: switched off (FSCNN_E2E_FUSED=0)");
-    return E_UNSUPPORTED;
-  }
-  if (!e2e_head_ok(pl.N, pl.net->num_classes, pl.H3, pl.W3, pl.H, h_out, w_out)) {
-    set_error("fscnn_forward_e2e: the tail does not take this geometry (C=%d, %dx%d from base %d, "
-              "low-res %dx%d)", pl.net->num_classes, h_out, w_out, pl.H, pl.H3, pl.W3);
-    return E_UNSUPPORTED;
-  }
-  void* xin = (char*)ws + e2e_x_offset(pl);
-  E2ePreArgs a{};
-  if (int rc = e2e_pre_args(x, channels_last, bgr, pl.N, h, w, pl.H, mean, std, xin, a)) return rc;
-  if (int rc = e2e_pre(a, x_dtype, pl.dtype, S(stream))) return rc;
+  const Plan& pl = plan->plan;
   RunArgs r{};
-  r.x = xin; r.x_dtype = pl.dtype; r.out = nullptr; r.out_dtype = pl.dtype;
-  r.P = params; r.R = running; r.NBT = nbt; r.ws = ws; r.momentum = 0.1f; r.st = S(stream);
+  r.P = params; r.R = running; r.NBT = nbt;
   r.e2e_ho = h_out; r.e2e_wo = w_out; r.e2e_softmax = softmax != 0; r.e2e_probs = probs;
   r.e2e_pdtype = probs_dtype; r.e2e_labels = labels; r.e2e_scale = label_scale;
-  GUARD(net_forward(plan->plan, r));
+  return forward_e2e_run("fscnn_forward_e2e", plan, x, x_dtype, channels_last, bgr, h, w, mean, std,
+                         e2e_head_ok(pl.N, pl.net->num_classes, pl.H3, pl.W3, pl.H, h_out, w_out),
+                         r, ws, stream);
+}
+
+// ---- bird's-eye tail (bev.hip) -------------------------------------------------------------------
+static int bev_args(const char* who, const double* m, int Hb, int Wb, int min_width,
+                    unsigned char* bev, int* rows, BevArgs& b) {
+  if (!m || !rows) {
+    set_error("%s: null argument", who);
+    return E_INVALID;
+  }
+  b.Hb = Hb; b.Wb = Wb; b.min_width = min_width; b.bev = bev; b.rows = rows;
+  for (int i = 0; i < 9; ++i) b.m[i] = m[i];
+  return OK;
+}
+
+int fscnn_bev_mask(const unsigned char* mask, int N, int h, int w, const double* m, int Hb, int Wb,
+                   int min_width, unsigned char* bev, int* rows, void* stream) {
+  BevArgs b{};
+  if (int rc = bev_args("fscnn_bev_mask", m, Hb, Wb, min_width, bev, rows, b)) return rc;
+  b.N = N; b.Ho = h; b.Wo = w;
+  return bev_mask(b, mask, S(stream));
+}
+
+int fscnn_e2e_bev(const void* logits, int dtype, int N, int Hc, int Wc, int C, int ldx, int base,
+                  int h, int w, int label_scale, const double* m, int Hb, int Wb, int min_width,
+                  unsigned char* bev, int* rows, void* stream) {
+  BevArgs b{};
+  if (int rc = bev_args("fscnn_e2e_bev", m, Hb, Wb, min_width, bev, rows, b)) return rc;
+  E2eHeadArgs a{};
+  a.N = N; a.Hl = Hc; a.Wl = Wc; a.C = C; a.base = base; a.Ho = h; a.Wo = w;
+  a.logits = logits; a.ldx = ldx; a.label_scale = label_scale;
+  return e2e_bev(a, b, dtype, S(stream));
+}
+
+int fscnn_forward_e2e_bev(const fscnn_plan* plan, const void* x, int x_dtype, int channels_last,
+                          int bgr, int h, int w, const float* mean, const float* std, int h_out,
+                          int w_out, int label_scale, const double* m, int Hb, int Wb,
+                          int min_width, unsigned char* bev, int* rows, const float* params,
+                          float* running, long long* nbt, void* ws, void* stream) {
+  if (!plan || !x || !params || !running || !ws) {
+    set_error("fscnn_forward_e2e_bev: null argument");
+    return E_INVALID;
+  }
+  BevArgs b{};
+  if (int rc = bev_args("fscnn_forward_e2e_bev", m, Hb, Wb, min_width, bev, rows, b)) return rc;
+  for (int i = 0; i < 9; ++i)
+    if (!std::isfinite(m[i])) {
+      set_error("fscnn_forward_e2e_bev: m[%d] is not finite", i);
+      return E_INVALID;
+    }
+  const Plan& pl = plan->plan;
+  RunArgs r{};
+  r.P = params; r.R = running; r.NBT = nbt;
+  r.e2e_ho = h_out; r.e2e_wo = w_out; r.e2e_scale = label_scale;
+  r.bev_hb = Hb; r.bev_wb = Wb; r.bev_min_width = min_width; r.bev_mask = bev; r.bev_rows = rows;
+  for (int i = 0; i < 9; ++i) r.bev_m[i] = m[i];
+  return forward_e2e_run("fscnn_forward_e2e_bev", plan, x, x_dtype, channels_last, bgr, h, w, mean,
+                         std, e2e_bev_ok(pl.N, pl.net->num_classes, pl.H3, pl.W3, pl.H, h_out,
+                                         w_out, Hb, Wb, min_width),
+                         r, ws, stream);
 }
 
 int fscnn_seg_metric(const void* pred, int pred_dtype, const long long* target, long long n,

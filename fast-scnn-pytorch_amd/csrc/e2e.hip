@@ -12,37 +12,11 @@
 // s is the rational ((2o + 1) in - out) / (2 out); cf_tap evaluates it in integers (quotient =
 // first tap, remainder / (2 out) = weight), so the taps are exact and the weight carries one fp32
 // rounding, and the host's tile bounds agree with the kernel's indices by construction.
-#include "kernels.hpp"
+#include "e2e_pixel.hpp"
 
 #include <algorithm>
 
 namespace fscnn {
-
-struct CfTap {
-  int i0, i1;
-  float w;  // weight of tap i1
-};
-// inv = 1.0 / (2 out): the double product lands within one of the quotient, which the remainder
-// test then settles exactly (numerators stay below 2^30: E2E_MAXDIM)
-__host__ __device__ __forceinline__ CfTap cf_tap(int o, int in, int out, double inv) {
-  int num = (2 * o + 1) * in - out;
-  num = num < 0 ? 0 : num;
-  const int d = 2 * out;
-  int q = (int)((double)num * inv);
-  int r = num - q * d;
-  if (r < 0) {
-    --q;
-    r += d;
-  } else if (r >= d) {
-    ++q;
-    r -= d;
-  }
-  CfTap t;
-  t.i0 = q;  // <= in - 1: num < 2 out in
-  t.i1 = q + 1 < in ? q + 1 : in - 1;
-  t.w = (float)r / (float)d;  // both exact in fp32 (d <= 2^15)
-  return t;
-}
 
 __device__ __forceinline__ float ld1(const uint8_t* p) { return (float)*p; }
 
@@ -142,10 +116,10 @@ int e2e_pre(const E2ePreArgs& a, int x_dtype, int y_dtype, hipStream_t st) {
 // those taps interpolate from, form one window (every index law here is monotone), staged once in
 // LDS class-major [row][C][WP] in fp32 like up_argmax's rows.  Per class a thread forms its four
 // base-grid taps exactly as up_nchw stores them (ac_lerp weights, lerp2 W-then-H, tap_as_stored),
-// combines them in fp32 and keeps the C values in registers (CB = the unrolled class bound) for
-// the max-subtracted softmax or the argmax (strict >: the lowest class wins ties).
+// combines them in fp32 (ee_pixel, e2e_pixel.hpp: shared with the bird's-eye tail) and keeps the
+// C values in registers (CB = the unrolled class bound) for the max-subtracted softmax or the
+// argmax (strict >: the lowest class wins ties).
 constexpr int EE_TW = 64, EE_TH = 4, EE_T = EE_TW * EE_TH;
-constexpr int EE_CMAX = 32;
 
 struct EeGeom {
   int rows, cols;  // largest staged window of any tile
@@ -167,36 +141,21 @@ static EeGeom ee_geom(int Hl, int Wl, int base, int Ho, int Wo) {
   return g;
 }
 
-// A tap as the forward stores it: lerp2(l0, x0, l1, x1) in the logits dtype.  fp32 and bf16 have
-// one answer.  fp16 has two: the fp32 value converted (two roundings), or v_fma_mixlo_f16, which
-// rounds the exact fma once, straight to fp16 -- what the compiler makes of f2h(fmaf(..)) where it
-// can -- and they differ by one fp16 ulp at a few values in 10^5.  up_nchw's stores use both: its
-// row-group kernel with vector stores (plans whose width is a multiple of 4) rounds once in column
-// 0 of each 4-vector and twice in columns 1 .. 3; its other forms round once everywhere (read from
-// the ISA of interp.hip; tests/test_gpu_e2e.py compares every tap with the stored logits).  Both
-// forms are spelled out here so that this kernel's own codegen has no say.
-template <typename TI>
-__device__ __forceinline__ float tap_as_stored(float l0, float x0, float l1, float x1, bool once) {
-  if constexpr (std::is_same<TI, f16>::value) {
-    const float p = l1 * x1;
-    if (once) {
-      uint32_t h;  // (the instruction writes the low half only)
-      asm("v_fma_mixlo_f16 %0, %1, %2, %3" : "=v"(h) : "v"(l0), "v"(x0), "v"(p));
-      return h2f((uint16_t)(h & 0xFFFFu));
-    }
-    float v = fmaf(l0, x0, p);
-    asm("" : "+v"(v));  // keeps the fp32 value apart from its conversion
-    return h2f(f2h(v));
-  } else {
-    return round_as<TI>(lerp2(l0, x0, l1, x1));
-  }
-}
-
 __device__ __forceinline__ void ee_store(void* p, int dtype, size_t i, float v) {
   if (dtype == DT_F32) ((float*)p)[i] = v;
   else if (dtype == DT_F16) st1((f16*)p + i, v);
   else st1((bf16*)p + i, v);
 }
+
+// the staged window as ee_pixel's row accessor: it starts at low-res row lo, column cl0
+struct EeLdsRows {
+  const float* w;
+  int lo, cl0, CWP, WP;
+  __device__ __forceinline__ int row(int r) const { return (r - lo) * CWP; }
+  __device__ __forceinline__ float at(int row, int c, int col) const {
+    return w[row + c * WP + (col - cl0)];
+  }
+};
 
 template <typename TI, int CB>
 __global__ __launch_bounds__(EE_T) void e2e_head_kernel(E2eHeadArgs a, int WP, double ih, double iw) {
@@ -223,47 +182,12 @@ __global__ __launch_bounds__(EE_T) void e2e_head_kernel(E2eHeadArgs a, int WP, d
   __syncthreads();
   const int xo = xo0 + threadIdx.x % EE_TW, yo = yo0 + threadIdx.x / EE_TW;
   if (xo > xo1 || yo > yo1) return;
-  const CfTap ty = cf_tap(yo, a.base, a.Ho, ih), tx = cf_tap(xo, a.base, a.Wo, iw);
-  Lerp lh[2] = {ac_lerp(ty.i0, a.Hl, a.base, sl_h), ac_lerp(ty.i1, a.Hl, a.base, sl_h)};
-  Lerp lw[2] = {ac_lerp(tx.i0, a.Wl, a.base, sl_w), ac_lerp(tx.i1, a.Wl, a.base, sl_w)};
-#pragma unroll
-  for (int k = 0; k < 2; ++k) {  // offsets into the staged window
-    lh[k].i0 = (lh[k].i0 - lo) * CWP;
-    lh[k].i1 = (lh[k].i1 - lo) * CWP;
-    lw[k].i0 -= cl0;
-    lw[k].i1 -= cl0;
-  }
-  const float wy0 = 1.0f - ty.w, wx0 = 1.0f - tx.w;
-  const bool once[2] = {a.f16_once || (tx.i0 & 3) == 0, a.f16_once || (tx.i1 & 3) == 0};
+  const EeGrid g{a.Hl, a.Wl, a.base, a.Ho, a.Wo, C, a.f16_once, ih, iw};
+  const EeLdsRows rows{ee_rows, lo, cl0, CWP, WP};
   float v[CB];
-#pragma unroll
-  for (int c = 0; c < CB; ++c) {
-    v[c] = -INFINITY;
-    if (c < C) {
-      const float* pc = ee_rows + c * WP;
-      float t[2][2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const float* r0 = pc + lh[i].i0;
-        const float* r1 = pc + lh[i].i1;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const float x0 = lerp2(lw[j].l0, r0[lw[j].i0], lw[j].l1, r0[lw[j].i1]);
-          const float x1 = lerp2(lw[j].l0, r1[lw[j].i0], lw[j].l1, r1[lw[j].i1]);
-          t[i][j] = tap_as_stored<TI>(lh[i].l0, x0, lh[i].l1, x1, once[j]);  // up_nchw's logit
-        }
-      }
-      v[c] = lerp2(wy0, lerp2(wx0, t[0][0], tx.w, t[0][1]), ty.w, lerp2(wx0, t[1][0], tx.w, t[1][1]));
-    }
-  }
-  float m = v[0];
-  int arg = 0;
-#pragma unroll
-  for (int c = 1; c < CB; ++c) {
-    const bool gt = v[c] > m;  // (classes >= C hold -inf and never win)
-    m = gt ? v[c] : m;
-    arg = gt ? c : arg;
-  }
+  ee_pixel<TI, CB>(g, xo, yo, rows, v);
+  float m;
+  const int arg = ee_argmax<CB>(v, m);
   const size_t pix = ((size_t)n * a.Ho + yo) * a.Wo + xo;
   if (a.labels) a.labels[pix] = (uint8_t)(arg * a.label_scale);
   if (!a.probs) return;
@@ -284,6 +208,12 @@ __global__ __launch_bounds__(EE_T) void e2e_head_kernel(E2eHeadArgs a, int WP, d
     if (c < C) ee_store(a.probs, a.probs_dtype, o0 + c * plane, v[c]);
 }
 
+int ee_f16_once(int N, int Hl, int Wl, int C, int base) {
+  UpArgs u{};
+  u.N = N; u.Hi = Hl; u.Wi = Wl; u.C = C; u.Ho = base; u.Wo = base;
+  return !(up_nchw_rows_path(u) && base % 4 == 0);
+}
+
 bool e2e_head_ok(int N, int C, int Hl, int Wl, int base, int Ho, int Wo) {
   if (N < 1 || N > 65535 || C < 1 || C > EE_CMAX || Hl < 1 || Wl < 1 || base < 1 || Ho < 1 ||
       Wo < 1 || base > E2E_MAXDIM || Ho > E2E_MAXDIM || Wo > E2E_MAXDIM)
@@ -294,11 +224,7 @@ bool e2e_head_ok(int N, int C, int Hl, int Wl, int base, int Ho, int Wo) {
 
 int e2e_head(const E2eHeadArgs& a0, int dtype, hipStream_t st) {
   E2eHeadArgs a = a0;
-  {
-    UpArgs u{};
-    u.N = a.N; u.Hi = a.Hl; u.Wi = a.Wl; u.C = a.C; u.Ho = a.base; u.Wo = a.base;
-    a.f16_once = !(up_nchw_rows_path(u) && a.base % 4 == 0);
-  }
+  a.f16_once = ee_f16_once(a.N, a.Hl, a.Wl, a.C, a.base);
   if (a.probs && (a.probs_dtype < DT_F32 || a.probs_dtype > DT_F16)) {
     set_error("e2e_head: probs dtype %d (0 fp32, 1 bf16, 2 fp16)", a.probs_dtype);
     return E_INVALID;

@@ -727,6 +727,24 @@ struct E2eHeadArgs {
 };
 bool e2e_head_ok(int N, int C, int Hl, int Wl, int base, int Ho, int Wo);
 int e2e_head(const E2eHeadArgs& a, int dtype, hipStream_t st);
+// Bird's-eye tail (bev.hip): nearest-neighbour perspective warp of a lane mask to Hb x Wb plus
+// the per-row table the centreline is read from (include/fastscnn.h: coordinate law, rows[4]).
+// The mask is either in memory (bev_mask) or evaluated per source pixel from the low-resolution
+// logits exactly as e2e_head's labels are (e2e_bev: E2eHeadArgs gives the geometry, label_scale
+// and the logits; its probs / labels are unused).
+constexpr int BEV_MAXW = 8192, BEV_MAXH = 65535;
+struct BevArgs {
+  int N, Ho, Wo;  // source mask size
+  int Hb, Wb, min_width;
+  double m[9];    // destination -> source
+  uint8_t* bev;   // [N][Hb][Wb] or null
+  int* rows;      // [N][Hb][4]: run_start, run_end, count, index_sum
+};
+bool bev_ok(int N, int Hb, int Wb, int min_width);
+bool e2e_bev_ok(int N, int C, int Hl, int Wl, int base, int Ho, int Wo, int Hb, int Wb,
+                int min_width);
+int bev_mask(const BevArgs& a, const uint8_t* mask, hipStream_t st);
+int e2e_bev(const E2eHeadArgs& h, const BevArgs& a, int dtype, hipStream_t st);
 int dropout(const DropArgs& a, int dtype, hipStream_t st);
 // GPU input path: ToTensor + Normalize of uint8 HWC images into NCHW (fp32 / bf16)
 int normalize_u8(const uint8_t* x, int N, int H, int W, const float* mean, const float* std,

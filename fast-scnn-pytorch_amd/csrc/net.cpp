@@ -1320,6 +1320,14 @@ struct Exec {
       h.Ho = r.e2e_ho; h.Wo = r.e2e_wo; h.logits = W(pl.logits); h.ldx = pl.Cp;
       h.softmax = r.e2e_softmax; h.probs = r.e2e_probs; h.probs_dtype = r.e2e_pdtype;
       h.labels = r.e2e_labels; h.label_scale = r.e2e_scale;
+      if (r.bev_rows) {
+        g_prof_tag = "head (e2e resample + bird's-eye rows)";
+        BevArgs b{};
+        b.Hb = r.bev_hb; b.Wb = r.bev_wb; b.min_width = r.bev_min_width;
+        for (int i = 0; i < 9; ++i) b.m[i] = r.bev_m[i];
+        b.bev = r.bev_mask; b.rows = r.bev_rows;
+        return e2e_bev(h, b, dt, r.st);
+      }
       return e2e_head(h, dt, r.st);
     }
     if (r.target) {
@@ -2008,6 +2016,11 @@ uint64_t fbits(float f) {
 
 std::vector<uint64_t> run_key(int kind, int s0, int s1, const RunArgs& r) {
   auto P = [](const void* p) { return (uint64_t)(uintptr_t)p; };
+  auto D = [](double d) {
+    uint64_t u;
+    memcpy(&u, &d, 8);
+    return u;
+  };
   return {(uint64_t)kind, (uint64_t)s0, (uint64_t)s1, P(r.x), (uint64_t)r.x_dtype, P(r.out),
           (uint64_t)r.out_dtype, P(r.aux_out), P(r.labels), (uint64_t)r.label_u8, P(r.P), P(r.R), P(r.NBT), P(r.G), P(r.ws),
           P(r.bws), P(r.dout), P(r.daux), fbits(r.dropout_p), fbits(r.momentum), P(r.target),
@@ -2016,7 +2029,9 @@ std::vector<uint64_t> run_key(int kind, int s0, int s1, const RunArgs& r) {
           fbits(r.alpha), fbits(r.gamma), P(r.head_ws), P(r.dice_stats), (uint64_t)r.validate,
           fbits(r.aux_weight), P(r.counts), (uint64_t)r.e2e_ho, (uint64_t)r.e2e_wo,
           (uint64_t)r.e2e_softmax, (uint64_t)r.e2e_pdtype, (uint64_t)r.e2e_scale, P(r.e2e_probs),
-          P(r.e2e_labels)};
+          P(r.e2e_labels), (uint64_t)r.bev_hb, (uint64_t)r.bev_wb, (uint64_t)r.bev_min_width,
+          P(r.bev_mask), P(r.bev_rows), D(r.bev_m[0]), D(r.bev_m[1]), D(r.bev_m[2]), D(r.bev_m[3]),
+          D(r.bev_m[4]), D(r.bev_m[5]), D(r.bev_m[6]), D(r.bev_m[7]), D(r.bev_m[8])};
 }
 
 template <typename F>

@@ -189,6 +189,13 @@ struct RunArgs {
   int e2e_ho = 0, e2e_wo = 0, e2e_softmax = 0, e2e_pdtype = 0, e2e_scale = 1;
   void* e2e_probs = nullptr;
   unsigned char* e2e_labels = nullptr;
+  // bird's-eye tail (bev.hip): with bev_rows != null the deployment tail is e2e_bev instead --
+  // the lane mask (argmax * e2e_scale at e2e_ho x e2e_wo) warped by bev_m (view -> frame) to
+  // bev_hb x bev_wb into bev_mask (or null) and its row table into bev_rows
+  int bev_hb = 0, bev_wb = 0, bev_min_width = 1;
+  double bev_m[9] = {};
+  unsigned char* bev_mask = nullptr;
+  int* bev_rows = nullptr;
   // backward: gradient of the input image, NCHW [N][3][H][W] in dx_dtype (autograd of x through
   // conv0, models/fast_scnn.py:153), or null
   void* dx = nullptr;

@@ -17,6 +17,11 @@ Same constructor arguments in the same order, same sub-module names (``backbone`
 (``csrc/e2e.hip``): the front end writes the backbone's input straight from the frame, and the
 tail reads the 1/8-resolution logits and writes only the ``input_size`` output -- neither the
 full-resolution logits nor, for ``predict``, any probability is ever formed.
+
+``bird_eye`` is a second tail (``csrc/bev.hip``) for what the car's code does next with the lane
+mask (``kuruma/vision/transform.py:130-201``, ``path_planning.py:188-293``): from the same
+1/8-resolution logits straight to the bird's-eye mask and the per-row table the centreline is
+read from (``bev.centerline``), without writing the frame-size mask.
 """
 import ctypes
 
@@ -25,9 +30,12 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
+from . import bev as _bev
 from .fast_scnn import E_UNSUPPORTED
 
 __all__ = ["EndToEndFastSCNN", "EndToEndPreprocessing"]
+
+_BEV_FUSED_MAX_PIXELS = 8 * 208 * 108  # bird_eye: largest measured total the fused tail won or tied
 
 _FRAME_DTYPES = {torch.uint8: _lib.DT_U8, torch.float32: _lib.DT_F32, torch.float16: _lib.DT_F16,
                  torch.bfloat16: _lib.DT_BF16}
@@ -211,3 +219,80 @@ class EndToEndFastSCNN(nn.Module):
         (kuruma/core/preprocessing.py:53-79).  Ties resolve to the lowest class, like
         ``torch.argmax``.  No probability tensor is written."""
         return self._run(frames, False, scale)
+
+    # ---- the bird's-eye tail ----------------------------------------------------------------------
+    @staticmethod
+    def _fused_view(n, hb, wb):
+        """Whether ``bird_eye`` takes the fused tail for a batch of ``n`` views of ``hb x wb``.
+        The fused tail evaluates the class scores once per view pixel, the two-launch route once
+        per frame pixel plus a byte gather per view pixel, so the fused tail pays while the views
+        are small.  Measured (profiles/bev_time.md, 640 x 360 frames): not slower up to
+        8 x 208 x 108 view pixels in all, slower from 1 x 1043 x 542 on; the rule keeps to what was
+        measured."""
+        return n * hb * wb <= _BEV_FUSED_MAX_PIXELS
+
+    def bird_eye(self, frames, view_params, scale=255, min_width=10, return_mask=True,
+                 fused=None):
+        """``(bev_mask, rows)``: the lane mask ``predict(frames, scale)`` warped to the bird's-eye
+        view of ``view_params`` (``BirdEyeView.params(..., source_size=input_size)[3]``: nearest
+        neighbour, border 0, like the reference's ``cv2.warpPerspective`` of the mask) as uint8
+        ``[N, Hb, Wb]`` (``None`` with ``return_mask=False``), and the int32 row table
+        ``[N, Hb, 4]`` = per row (run_start, run_end, count, index_sum) of the non-zero pixels:
+        the longest run of at least ``min_width`` (leftmost on ties, ``0, 0`` for none), and the
+        count and the sum of the column indices; ``bev.centerline`` turns it into either
+        centreline of the reference.  One launch after the backbone; the frame-size mask is not
+        written.  Views wider than 8192 or taller than 65535 pixels are refused.
+
+        ``fused``: ``None`` picks the route (``_fused_view``: the fused tail for small views,
+        ``predict`` followed by ``fscnn_bev_mask`` for large ones, as measured), ``True`` /
+        ``False`` force one; both give the same bits.  ``_last_fused`` tells which one ran."""
+        wb, hb = (int(v) for v in view_params["output_size"])
+        min_width = int(min_width)
+        if not (1 <= wb <= _bev.MAX_WIDTH and 1 <= hb <= _bev.MAX_HEIGHT) or min_width < 1:
+            raise RuntimeError("EndToEndFastSCNN.bird_eye: view %d x %d, min_width %d: the "
+                               "bird's-eye tail takes widths 1 .. %d, heights 1 .. %d and "
+                               "min_width >= 1" % (wb, hb, min_width, _bev.MAX_WIDTH,
+                                                   _bev.MAX_HEIGHT))
+        frames, N, h, w = self._check(frames)
+        if N > 65535:
+            raise RuntimeError("EndToEndFastSCNN.bird_eye: batch %d above 65535" % N)
+        m = _bev.inverse_map(view_params)
+        bb, dev = self.backbone, frames.device
+        dt = self._compute_dtype()
+        wo, ho = int(self.input_size[0]), int(self.input_size[1])
+        base = self.base_size
+        with torch.no_grad():
+            nat = bb.native()
+            ar = bb._exec_arena(dev)
+            if ar["P"].device != dev:
+                raise RuntimeError("EndToEndFastSCNN: frames on %s but parameters on %s"
+                                   % (dev, ar["P"].device))
+            plan, _, _ = nat.plan(N, base, base, _lib.dtype_code(dt), False, dev)
+            lib = _lib.load()
+            need = int(lib.fscnn_e2e_ws_bytes(plan))
+            if need < 0:
+                _lib.check(need, "fscnn_e2e_ws_bytes")
+            ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+            mask = torch.empty((N, hb, wb), dtype=torch.uint8, device=dev) if return_mask else None
+            rows = torch.empty((N, hb, 4), dtype=torch.int32, device=dev)
+            m9 = (ctypes.c_double * 9)(*[float(v) for v in m])
+            hm, hs = self._norm_host()
+            if fused is None:
+                fused = self._fused_view(N, hb, wb)
+            rc = E_UNSUPPORTED
+            with torch.cuda.device(dev):
+                if fused:
+                    rc = lib.fscnn_forward_e2e_bev(
+                        plan, _lib.ptr(frames), _FRAME_DTYPES[frames.dtype],
+                        int(self.channels_last), int(self.bgr), h, w, hm, hs, ho, wo,
+                        int(scale) & 255, m9, hb, wb, min_width, _lib.ptr(mask), _lib.ptr(rows),
+                        _lib.ptr(ar["P"]), _lib.ptr(ar["R"]), _lib.ptr(ar["NBT"]), _lib.ptr(ws),
+                        _lib.stream_ptr(dev))
+            fused = rc != E_UNSUPPORTED  # nothing was launched: the geometry check comes first
+            if fused:
+                _lib.check(rc, "fscnn_forward_e2e_bev")
+        if not fused:  # by choice, FSCNN_E2E_FUSED=0, more than 32 classes: the mask, then the warp
+            mask, rows = _bev.warp_mask(self.predict(frames, scale), m, (wb, hb), min_width,
+                                        return_mask)
+        object.__setattr__(self, "_last_fused", fused)
+        return mask, rows

@@ -178,6 +178,51 @@ int fscnn_forward_e2e(const fscnn_plan* plan, const void* x, int x_dtype, int ch
                       int w_out, int softmax, void* probs, int probs_dtype, unsigned char* labels,
                       int label_scale, const float* params, float* running, long long* nbt,
                       void* ws, void* stream);
+/* Bird's-eye tail of the deployment pipeline: what the reference's consumers do to the lane mask
+ * before anything is steered -- the nearest-neighbour perspective warp to the bird's-eye view
+ * (PerspectiveTransformer.transform_image_and_mask, kuruma/vision/transform.py:130-201) and the
+ * per-row scan of the warped mask (PathPlanner.extract_centerline / extract_centerline_fast,
+ * kuruma/vision/path_planning.py:188-293) -- in one launch, one workgroup per bird's-eye row.
+ *
+ * Coordinate law.  m[9]: HOST doubles, the destination -> source matrix (the inverse of the
+ * matrix cv2.warpPerspective is given), all finite, otherwise -1.  For destination pixel (x, y),
+ * in fp64, every operation rounded on its own (no fused multiply-add):
+ *     X = (m0*x + m1*y) + m2      Y = (m3*x + m4*y) + m5      W = (m6*x + m7*y) + m8
+ *     W = (W != 0) ? 1.0 / W : 0
+ *     fx = max(INT_MIN, min(INT_MAX, X*W))  (a NaN product counts as INT_MAX)
+ *     sx = rint(fx)  (half to even);  fy, sy the same from Y
+ * The pixel takes the source value at (sx, sy) when 0 <= sx < w and 0 <= sy < h, else 0.  This is
+ * the shape of OpenCV's classic nearest-neighbour perspective warp with a constant 0 border;
+ * bit parity with a particular OpenCV build is not claimed.
+ *
+ * Outputs.  bev: uint8 [N][Hb][Wb], may be null.  rows: int32 [N][Hb][4] per bird's-eye row:
+ *   [0], [1]  run_start, run_end (exclusive) of the longest run of non-zero pixels of length
+ *             >= min_width, the leftmost of equally long runs; 0, 0 when there is none
+ *             (centre of the exact centreline: (run_start + run_end) / 2, rounded down)
+ *   [2], [3]  count of non-zero pixels and the sum of their column indices (the fast
+ *             centreline: index_sum / count, rounded down, where count >= min_width)
+ * Exact, deterministic, no atomics.
+ * Limits: 1 <= N <= 65535, 1 <= Wb <= 8192, 1 <= Hb <= 65535, min_width >= 1; the logits source
+ * additionally needs 1 <= C <= 32 and every size <= 16384.  Outside them: -2, nothing launched.
+ *
+ * fscnn_bev_mask: source (a), a uint8 mask [N][h][w] in device memory.
+ * fscnn_e2e_bev: source (b), the low-resolution logits of an inference plan as fscnn_e2e_head
+ *   takes them; the value at (sx, sy) is (argmax * label_scale) mod 256, evaluated exactly as
+ *   fscnn_e2e_head evaluates its label at output pixel (sx, sy) of an h x w output (same code).
+ *   The h x w mask itself is never written.
+ * fscnn_forward_e2e_bev: front end, backbone and the bird's-eye tail on `stream`; plan, frames
+ *   and ws (fscnn_e2e_ws_bytes) as fscnn_forward_e2e.  Returns -2 before any launch outside the
+ *   limits above and when FSCNN_E2E_FUSED=0, like fscnn_forward_e2e. */
+int fscnn_bev_mask(const unsigned char* mask, int N, int h, int w, const double* m, int Hb, int Wb,
+                   int min_width, unsigned char* bev, int* rows, void* stream);
+int fscnn_e2e_bev(const void* logits, int dtype, int N, int Hc, int Wc, int C, int ldx, int base,
+                  int h, int w, int label_scale, const double* m, int Hb, int Wb, int min_width,
+                  unsigned char* bev, int* rows, void* stream);
+int fscnn_forward_e2e_bev(const fscnn_plan* plan, const void* x, int x_dtype, int channels_last,
+                          int bgr, int h, int w, const float* mean, const float* std, int h_out,
+                          int w_out, int label_scale, const double* m, int Hb, int Wb,
+                          int min_width, unsigned char* bev, int* rows, const float* params,
+                          float* running, long long* nbt, void* ws, void* stream);
 
 /* SegmentationMetric counters (utils/metric.py:73-105, batch_pix_accuracy +
  * batch_intersection_union) of n predictions (pred_dtype 0 int64, 1 uint8) against int64 labels,
