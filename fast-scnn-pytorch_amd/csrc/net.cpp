@@ -161,6 +161,8 @@ struct Alloc {
 
 int dwout(int h, int s) { return (h - 1) / s + 1; }
 
+constexpr size_t OWN = (size_t)-1;  // no override: the tensor gets a buffer of its own
+
 }  // namespace
 
 // FSCNN_IR_S2=0: the stride-2 bottlenecks (1.0, 2.0) as three unfused launches in inference
@@ -170,17 +172,16 @@ static bool ir_stride2_enabled() {
 }
 // shape of bottleneck i as one fused inference launch (ir.hip); false when the block runs as
 // its three unfused units (training plans, unsupported shapes)
-bool ir_block_shape(const Net& net, const Plan& pl, int i, IrArgs& b) {
-  const LbL& l = net.lb[i];
+bool ir_block_shape(const Plan& pl, int i, IrArgs& b) {
+  const LbL& l = pl.net->lb[i];
+  const Unit& ud = pl.lbd[i];
   if (pl.train || (l.stride != 1 && l.stride != 2)) return false;
   b = IrArgs{};
   b.N = pl.N;
   b.stride = l.stride;
-  b.H = i < 3 ? pl.H4 : pl.H5;
-  b.W = i < 3 ? pl.W4 : pl.W5;
+  b.H = ud.Ho; b.W = ud.Wo;
   // input map: the previous block's output, or (block 0) the LearningToDownsample output
-  b.Hi = i == 0 ? pl.H3 : (i < 4 ? pl.H4 : pl.H5);
-  b.Wi = i == 0 ? pl.W3 : (i < 4 ? pl.W4 : pl.W5);
+  b.Hi = ud.Hi; b.Wi = ud.Wi;
   b.Cin = l.cin; b.E = l.cin * 6; b.Cout = l.cout;
   b.ldx = i == 0 ? pl.l2pw.ld : pl.lbp[i - 1].ld; b.ldy = pl.lbp[i].ld;
   b.residual = l.stride == 1 && l.cin == l.cout;
@@ -218,89 +219,107 @@ int plan_build(const Net& net, int N, int H, int W, int dtype, int train, Plan& 
   const size_t E = dtype == DT_F32 ? 4 : 2;
   pl.Cp = (net.num_classes + V - 1) / V * V;
   Alloc A, B;  // forward (saved) and backward (scratch) workspaces
-  auto unit = [&](Unit& u, long long M, int C, int nparts, size_t a_override = (size_t)-1,
-                  int ld = 0) {
+  // One statement per unit says everything about it: its debug key, its label (the module path
+  // in models/fast_scnn.py), its layer, its geometry and whether its activation is stored.
+  auto unit = [&](Unit& u, int kind, const std::string& key, const std::string& name,
+                  const ConvL& c, const BnL& bn, long long M, int nparts, bool lazy,
+                  size_t a_override, int ld) {
+    u.kind = kind; u.key = key; u.name = name; u.conv = &c; u.bn = &bn; u.lazy = lazy;
+    const int C = bn.C;
     u.M = M; u.C = C; u.ld = ld ? ld : C;
-    u.a = a_override != (size_t)-1 ? a_override : A.get((size_t)M * u.ld * E);
+    u.a = a_override != OWN ? a_override : A.get((size_t)M * u.ld * E);
     u.z = train ? A.get((size_t)M * C * E) : u.a;
     u.nparts = nparts;
     if (train) u.part = A.get((size_t)nparts * 3 * C * 4);
     u.mean = A.get(C * 4); u.invstd = A.get(C * 4);
     u.scale = A.get(C * 4); u.shift = A.get(C * 4);
   };
-  auto gunit = [&](Unit& u, size_t ga_override = (size_t)-1, int ld = 0) {
+  auto pw_unit = [&](Unit& u, const std::string& key, const std::string& name, const ConvL& c,
+                     const BnL& bn, long long M, bool lazy, size_t a_override = OWN,
+                     int ld = 0) {
+    unit(u, U_PW, key, name, c, bn, M, gemm_parts((int)M), lazy, a_override, ld);
+  };
+  // depthwise 3x3 on an Hi x Wi map
+  auto dw_unit = [&](Unit& u, const std::string& key, const std::string& name, const ConvL& c,
+                     const BnL& bn, int Hi, int Wi, int stride, bool lazy) {
+    u.Hi = Hi; u.Wi = Wi; u.stride = stride;
+    u.Ho = dwout(Hi, stride); u.Wo = dwout(Wi, stride);
+    unit(u, U_DW, key, name, c, bn, (long long)N * u.Ho * u.Wo,
+         dw_parts(N, u.Ho, u.Wo, bn.C, dtype, stride), lazy, OWN, 0);
+  };
+  auto gunit = [&](Unit& u, size_t ga_override = OWN, int ld = 0) {
     u.ga_ld = ld ? ld : u.C;
-    u.ga = ga_override != (size_t)-1 ? ga_override : B.get((size_t)u.M * u.ga_ld * E);
+    u.ga = ga_override != OWN ? ga_override : B.get((size_t)u.M * u.ga_ld * E);
   };
   const long long M0 = (long long)N * pl.H1 * pl.W1, M1 = (long long)N * pl.H2 * pl.W2,
-                  M2 = (long long)N * pl.H3 * pl.W3, M4 = (long long)N * pl.H4 * pl.W4,
-                  M5 = (long long)N * pl.H5 * pl.W5;
+                  M2 = (long long)N * pl.H3 * pl.W3, M5 = (long long)N * pl.H5 * pl.W5;
   if (M0 > 0x7fffffffLL / 32) {
     set_error("plan_build: batch too large for 32-bit row indexing");
     return E_INVALID;
   }
   if (dtype != DT_F32) pl.pbf = A.get((size_t)net.p_total * 2);  // 16-bit weight copy
   if (train) pl.wt = A.get((size_t)net.wt_total * E);
-  unit(pl.c0, M0, 32, conv0_parts(N, pl.H1, pl.W1));
-  unit(pl.l1dw, M1, 32, dw_parts(N, pl.H2, pl.W2, 32, dtype, 2));
-  unit(pl.l1pw, M1, 48, gemm_parts((int)M1));
-  unit(pl.l2dw, M2, 48, dw_parts(N, pl.H3, pl.W3, 48, dtype, 2));
-  unit(pl.l2pw, M2, 64, gemm_parts((int)M2));
+  // train: BN+ReLU outputs whose only consumers are GEMM / depthwise operands (and the wgrads
+  // reading them again in the backward) are never stored: bn_apply is skipped and the consumers
+  // apply relu(fmaf(z, scale, shift)) while staging.  Saves a read + write of each tensor per step.
+  const bool LAZY = train != 0, STORED = false;
+  // The forward workspace, in forward order.  This stays an explicit sequence: the units'
+  // buffers interleave with the tensors between them (concat, pooled, feats_a, up_low, f, ...),
+  // and some units' activations alias those (a_override).
+  unit(pl.c0, U_CONV0, "c0", "learning_to_downsample.conv", net.c0, net.b0, M0,
+       conv0_parts(N, pl.H1, pl.W1), LAZY, OWN, 0);
+  dw_unit(pl.l1dw, "l1dw", "learning_to_downsample.dsconv1.dw", net.ltd1.dw, net.ltd1.bdw,
+          pl.H1, pl.W1, 2, LAZY);
+  pw_unit(pl.l1pw, "l1pw", "learning_to_downsample.dsconv1.pw", net.ltd1.pw, net.ltd1.bpw, M1, LAZY);
+  dw_unit(pl.l2dw, "l2dw", "learning_to_downsample.dsconv2.dw", net.ltd2.dw, net.ltd2.bdw,
+          pl.H2, pl.W2, 2, LAZY);
+  // LearningToDownsample's output: read by bottleneck1.0's expand and the FFM's high-res
+  // branch (both GEMM operands) — unless the aux head's im2col reads it as well
+  pw_unit(pl.l2pw, "l2pw", "learning_to_downsample.dsconv2.pw", net.ltd2.pw, net.ltd2.bpw, M2,
+          net.aux ? STORED : LAZY);
   pl.concat = A.get((size_t)M5 * 256 * E);
+  int Hc = pl.H3, Wc = pl.W3;  // the bottlenecks' running map: H3 -> H4 (block 0) -> H5 (block 3)
   for (int i = 0; i < 9; ++i) {
     const LbL& l = net.lb[i];
-    long long Min = i == 0 ? M2 : (i <= 3 ? M4 : M5);
-    long long Mout = i < 3 ? M4 : M5;
-    int Ho = i < 3 ? pl.H4 : pl.H5, Wo = i < 3 ? pl.W4 : pl.W5;
-    int e = l.cin * 6;
-    unit(pl.lbe[i], Min, e, gemm_parts((int)Min));
-    unit(pl.lbd[i], Mout, e, dw_parts(N, Ho, Wo, e, dtype, l.stride));
-    if (i == 8) unit(pl.lbp[i], Mout, l.cout, gemm_parts((int)Mout), pl.concat, 256);
-    else unit(pl.lbp[i], Mout, l.cout, gemm_parts((int)Mout));
+    const std::string k = std::to_string(i);
+    const std::string b = "global_feature_extractor.bottleneck" + std::to_string(i / 3 + 1) + "." +
+                          std::to_string(i % 3);
+    pw_unit(pl.lbe[i], "lbe" + k, b + ".expand", l.e, l.be, (long long)N * Hc * Wc, LAZY);
+    dw_unit(pl.lbd[i], "lbd" + k, b + ".dw", l.d, l.bd, Hc, Wc, l.stride, LAZY);
+    // the last block writes the first 128 channels of the PPM's concat buffer
+    pw_unit(pl.lbp[i], "lbp" + k, b + ".project", l.p, l.bp, pl.lbd[i].M, STORED,
+            i == 8 ? pl.concat : OWN, i == 8 ? 256 : 0);
+    pl.lbp[i].block_name = b + " (fused block)";
+    Hc = pl.lbd[i].Ho; Wc = pl.lbd[i].Wo;
   }
   // PPM: pooled / feats are bin-major [50][N][C]
   pl.pooled = A.get((size_t)50 * N * 128 * E);
   pl.feats_a = A.get((size_t)50 * N * 32 * E);
-  static const int kk[4] = {1, 2, 3, 6}, base[4] = {0, 1, 5, 14};
-  for (int i = 0; i < 4; ++i) {
-    long long M = (long long)kk[i] * kk[i] * N;
-    unit(pl.ppk[i], M, 32, gemm_parts((int)M), pl.feats_a + (size_t)base[i] * N * 32 * E, 32);
-  }
-  unit(pl.po, M5, 128, gemm_parts((int)M5));
+  for (int i = 0; i < 4; ++i)
+    pw_unit(pl.ppk[i], "ppk" + std::to_string(i),
+            "global_feature_extractor.ppm.conv" + std::to_string(i + 1), net.ppm_c[i], net.ppm_b[i],
+            (long long)PPM_BINS[i] * PPM_BINS[i] * N, STORED,
+            pl.feats_a + (size_t)PPM_BASE[i] * N * 32 * E, 32);
+  pw_unit(pl.po, "po", "global_feature_extractor.ppm.out", net.ppm_o, net.ppm_ob, M5, STORED);
   pl.up_low = A.get((size_t)M2 * 128 * E);
-  unit(pl.fdw, M2, 128, dw_parts(N, pl.H3, pl.W3, 128, dtype, 1));
+  dw_unit(pl.fdw, "fdw", "feature_fusion.dwconv", net.ffm_dw, net.ffm_bdw, pl.H3, pl.W3, 1, LAZY);
   pl.f = A.get((size_t)M2 * 128 * E);
-  unit(pl.flow, M2, 128, gemm_parts((int)M2), pl.f);    // a = f (combined), z own
-  unit(pl.fhigh, M2, 128, gemm_parts((int)M2), pl.f);
-  unit(pl.c1dw, M2, 128, dw_parts(N, pl.H3, pl.W3, 128, dtype, 1));
-  unit(pl.c1pw, M2, 128, gemm_parts((int)M2));
-  unit(pl.c2dw, M2, 128, dw_parts(N, pl.H3, pl.W3, 128, dtype, 1));
-  unit(pl.c2pw, M2, 128, gemm_parts((int)M2));
+  // both FFM branches: a = f (combined), z own
+  pw_unit(pl.flow, "flow", "feature_fusion.conv_lower_res", net.ffm_low, net.ffm_blow, M2, STORED, pl.f);
+  pw_unit(pl.fhigh, "fhigh", "feature_fusion.conv_higher_res", net.ffm_high, net.ffm_bhigh, M2,
+          STORED, pl.f);
+  dw_unit(pl.c1dw, "c1dw", "classifier.dsconv1.dw", net.cls1.dw, net.cls1.bdw, pl.H3, pl.W3, 1, LAZY);
+  pw_unit(pl.c1pw, "c1pw", "classifier.dsconv1.pw", net.cls1.pw, net.cls1.bpw, M2, LAZY);
+  dw_unit(pl.c2dw, "c2dw", "classifier.dsconv2.dw", net.cls2.dw, net.cls2.bdw, pl.H3, pl.W3, 1, LAZY);
+  pw_unit(pl.c2pw, "c2pw", "classifier.dsconv2.pw", net.cls2.pw, net.cls2.bpw, M2, STORED);
   pl.drop = train ? A.get((size_t)M2 * 128 * E) : pl.c2pw.a;
   pl.logits = A.get((size_t)M2 * pl.Cp * E);
   if (net.aux) {  // models/fast_scnn.py:24-31: 3x3 conv on im2col columns, BN, ReLU, Dropout, 1x1
-    unit(pl.aux0, M2, 32, gemm_parts((int)M2));
+    pw_unit(pl.aux0, "aux0", "auxlayer", net.aux0, net.aux1, M2, STORED);
     pl.aux_col = A.get((size_t)M2 * 576 * E);
     pl.aux_drop = train ? A.get((size_t)M2 * 32 * E) : pl.aux0.a;
     pl.aux_logits = A.get((size_t)M2 * pl.Cp * E);
   }
-  // labels: models/fast_scnn.py module paths
-  pl.c0.name = "learning_to_downsample.conv";
-  pl.l1dw.name = "learning_to_downsample.dsconv1.dw"; pl.l1pw.name = "learning_to_downsample.dsconv1.pw";
-  pl.l2dw.name = "learning_to_downsample.dsconv2.dw"; pl.l2pw.name = "learning_to_downsample.dsconv2.pw";
-  for (int i = 0; i < 9; ++i) {
-    const std::string b = "global_feature_extractor.bottleneck" + std::to_string(i / 3 + 1) + "." +
-                          std::to_string(i % 3);
-    pl.lbe[i].name = b + ".expand"; pl.lbd[i].name = b + ".dw"; pl.lbp[i].name = b + ".project";
-    pl.lbp[i].block_name = b + " (fused block)";
-  }
-  for (int i = 0; i < 4; ++i) pl.ppk[i].name = "global_feature_extractor.ppm.conv" + std::to_string(i + 1);
-  pl.po.name = "global_feature_extractor.ppm.out";
-  pl.fdw.name = "feature_fusion.dwconv"; pl.flow.name = "feature_fusion.conv_lower_res";
-  pl.fhigh.name = "feature_fusion.conv_higher_res";
-  pl.c1dw.name = "classifier.dsconv1.dw"; pl.c1pw.name = "classifier.dsconv1.pw";
-  pl.c2dw.name = "classifier.dsconv2.dw"; pl.c2pw.name = "classifier.dsconv2.pw";
-  pl.aux0.name = "auxlayer";
   if (train) {
     pl.g_raw = A.get((size_t)2 * M2 * pl.Cp * 4);  // own-row plane + row-spill plane
     pl.head_part = A.get((size_t)ce_head_parts(N, pl.H3, pl.W3) * 2 * 4);
@@ -314,23 +333,12 @@ int plan_build(const Net& net, int N, int H, int W, int dtype, int train, Plan& 
     pl.fcnt = A.get(2 * BN_COUNTERS * 4);
     pl.bcnt = pl.fcnt + BN_COUNTERS * 4;
   }
-  if (train) {
-    // BN+ReLU outputs whose only consumers are GEMM / depthwise operands (and the wgrads reading
-    // them again in the backward) are never stored: bn_apply is skipped and the consumers apply
-    // relu(fmaf(z, scale, shift)) while staging.  Saves a read + write of each tensor per step.
-    pl.c0.lazy = pl.l1dw.lazy = pl.l1pw.lazy = pl.l2dw.lazy = true;
-    for (int i = 0; i < 9; ++i) pl.lbe[i].lazy = pl.lbd[i].lazy = true;
-    pl.fdw.lazy = pl.c1dw.lazy = pl.c1pw.lazy = pl.c2dw.lazy = true;
-    // LearningToDownsample's output: read by bottleneck1.0's expand and the FFM's high-res
-    // branch (both GEMM operands) — unless the aux head's im2col reads it as well
-    if (!net.aux) pl.l2pw.lazy = true;
-  }
   // fp32 inference: the fused bottlenecks' expand / project weights as three bf16 split planes
   // (weights_prep mode 3, once per forward), so the fused kernel does no split arithmetic
   if (!train && dtype == DT_F32) {
     for (int i = 0; i < 9; ++i) {
       IrArgs b;
-      if (!ir_block_shape(net, pl, i, b)) continue;
+      if (!ir_block_shape(pl, i, b)) continue;
       pl.lb_we3[i] = A.get((size_t)3 * b.E * b.Cin * 2);
       pl.lb_wp3[i] = A.get((size_t)3 * b.Cout * b.E * 2);
     }
@@ -342,24 +350,14 @@ int plan_build(const Net& net, int N, int H, int W, int dtype, int train, Plan& 
   auto nm = [&](const char* n, size_t off, long long rows, int cols, int ld, int bws) {
     pl.named.push_back({n, off, rows, cols, ld, bws});
   };
-  auto nu = [&](const std::string& n, const Unit& u) {
-    pl.named.push_back({n + ".a", u.a, u.M, u.C, u.ld, 0});
-    pl.named.push_back({n + ".z", u.z, u.M, u.C, u.C, 0});
-    pl.named.push_back({n + ".scale", u.scale, 1, u.C, u.C, 0});
-    pl.named.push_back({n + ".shift", u.shift, 1, u.C, u.C, 0});
-    pl.named.push_back({n + ".mean", u.mean, 1, u.C, u.C, 0});
-    pl.named.push_back({n + ".invstd", u.invstd, 1, u.C, u.C, 0});
-  };
-  nu("c0", pl.c0); nu("l1dw", pl.l1dw); nu("l1pw", pl.l1pw); nu("l2dw", pl.l2dw); nu("l2pw", pl.l2pw);
-  for (int i = 0; i < 9; ++i) {
-    nu("lbe" + std::to_string(i), pl.lbe[i]);
-    nu("lbd" + std::to_string(i), pl.lbd[i]);
-    nu("lbp" + std::to_string(i), pl.lbp[i]);
-  }
-  for (int i = 0; i < 4; ++i) nu("ppk" + std::to_string(i), pl.ppk[i]);
-  nu("po", pl.po); nu("fdw", pl.fdw); nu("flow", pl.flow); nu("fhigh", pl.fhigh);
-  nu("c1dw", pl.c1dw); nu("c1pw", pl.c1pw); nu("c2dw", pl.c2dw); nu("c2pw", pl.c2pw);
-  if (net.aux) nu("aux0", pl.aux0);
+  for_each_unit(pl, [&](const Unit& u) {
+    pl.named.push_back({u.key + ".a", u.a, u.M, u.C, u.ld, 0});
+    pl.named.push_back({u.key + ".z", u.z, u.M, u.C, u.C, 0});
+    pl.named.push_back({u.key + ".scale", u.scale, 1, u.C, u.C, 0});
+    pl.named.push_back({u.key + ".shift", u.shift, 1, u.C, u.C, 0});
+    pl.named.push_back({u.key + ".mean", u.mean, 1, u.C, u.C, 0});
+    pl.named.push_back({u.key + ".invstd", u.invstd, 1, u.C, u.C, 0});
+  });
   nm("concat", pl.concat, M5, 256, 256, 0);
   nm("up_low", pl.up_low, M2, 128, 128, 0);
   nm("f", pl.f, M2, 128, 128, 0);
@@ -368,6 +366,9 @@ int plan_build(const Net& net, int N, int H, int W, int dtype, int train, Plan& 
 
   if (train) {
     const int C = net.num_classes;
+    // The gradient buffers, in backward order (lbd, lbe, lbp per block).  The second explicit
+    // sequence: g_f, g_up, g_concat, ... lie between the units', and lbp8 / the PPM branches
+    // alias g_concat / g_feats.
     pl.g_logits = B.get((size_t)M2 * pl.Cp * E);
     pl.t_up = B.get((size_t)N * C * H * pl.W3 * 4);
     pl.g_drop = B.get((size_t)M2 * 128 * E);
@@ -383,13 +384,12 @@ int plan_build(const Net& net, int N, int H, int W, int dtype, int train, Plan& 
     pl.g_concat = B.get((size_t)M5 * 256 * E);
     pl.g_feats = B.get((size_t)50 * N * 32 * E);
     for (int i = 0; i < 4; ++i)
-      gunit(pl.ppk[i], pl.g_feats + (size_t)base[i] * N * 32 * E, 32);
+      gunit(pl.ppk[i], pl.g_feats + (size_t)PPM_BASE[i] * N * 32 * E, 32);
     pl.g_pooled = B.get((size_t)50 * N * 128 * E);
     for (int i = 8; i >= 0; --i) {
       gunit(pl.lbd[i]);
       gunit(pl.lbe[i]);
-      if (i == 8) gunit(pl.lbp[i], pl.g_concat, 256);
-      else gunit(pl.lbp[i]);
+      gunit(pl.lbp[i], i == 8 ? pl.g_concat : OWN, i == 8 ? 256 : 0);
     }
     gunit(pl.l2pw);
     gunit(pl.l2dw);
@@ -402,89 +402,50 @@ int plan_build(const Net& net, int N, int H, int W, int dtype, int train, Plan& 
       pl.g_aux = B.get((size_t)M2 * 32 * E);
       pl.aux_dcol = B.get((size_t)M2 * 576 * E);
     }
-    // scratch sized for the largest consumer
-    long long max_mc = 0;
-    auto upd = [&](const Unit& u) { if (u.M * u.C > max_mc) max_mc = u.M * u.C; };
-    upd(pl.c0); upd(pl.l1dw); upd(pl.l1pw); upd(pl.l2dw); upd(pl.l2pw);
-    for (int i = 0; i < 9; ++i) { upd(pl.lbe[i]); upd(pl.lbd[i]); upd(pl.lbp[i]); }
-    upd(pl.po); upd(pl.fdw); upd(pl.flow); upd(pl.c1dw); upd(pl.c1pw);
-    if (net.aux) upd(pl.aux0);
     // BN-backward outputs: one slot per unit per backward call (Exec::dz_buf), so a wgrad
     // queued for the side stream never races a later rewrite
     size_t dzs = 0;
-    auto dzu = [&](const Unit& u) { dzs += ((size_t)u.M * u.C * E + 255) / 256 * 256; };
-    dzu(pl.c0); dzu(pl.l1dw); dzu(pl.l1pw); dzu(pl.l2dw); dzu(pl.l2pw);
-    for (int i = 0; i < 9; ++i) { dzu(pl.lbe[i]); dzu(pl.lbd[i]); dzu(pl.lbp[i]); }
-    for (int i = 0; i < 4; ++i) dzu(pl.ppk[i]);
-    dzu(pl.po); dzu(pl.fdw); dzu(pl.flow); dzu(pl.fhigh); dzu(pl.c1dw); dzu(pl.c1pw);
-    dzu(pl.c2dw); dzu(pl.c2pw);
-    if (net.aux) dzu(pl.aux0);
-    (void)max_mc;
+    for_each_unit(pl, [&](const Unit& u) { dzs += ((size_t)u.M * u.C * E + 255) / 256 * 256; });
     pl.dz_bytes = dzs;
     pl.dz = B.get(dzs);
     // weight-gradient partial slabs: the reductions of a backward stage are deferred to one
     // multi-job launch pair (Exec::flush_reduce), so every job keeps its own slab until then;
-    // the arena holds the whole step's (sum over jobs, 64-float aligned each)
+    // the arena holds the whole step's (sum over jobs, 64-float aligned each).  Each unit's share
+    // is what Exec::pw_bwd / dw_bwd will ask for, from the same conv and geometry.
     size_t slab = 0;
     auto add_slab = [&](size_t floats) { slab += (floats + 63) / 64 * 64; };
-    auto pw_slab = [&](long long M, int n, int k, bool bias = false) {
-      add_slab((size_t)gemm_tn_splits((int)M, n, k) * n * k);
-      if (bias) add_slab((size_t)colsum_parts((int)M) * n);
+    auto pw_slab = [&](const ConvL& c, long long M) {
+      const int k = c.cin * c.k * c.k;
+      add_slab((size_t)gemm_tn_splits((int)M, c.cout, k) * c.cout * k);
+      if (c.b >= 0) add_slab((size_t)colsum_parts((int)M) * c.cout);
     };
-    auto dw_slab = [&](int Ho, int Wo, int Cc, int st) {
-      add_slab((size_t)dw_wgrad_parts(N, Ho, Wo, Cc, dtype, st) * 9 * Cc);
-    };
-    pw_slab(M1, 48, 32); pw_slab(M2, 64, 48);
-    dw_slab(pl.H2, pl.W2, 32, 2); dw_slab(pl.H3, pl.W3, 48, 2);
-    for (int i = 0; i < 9; ++i) {
-      const LbL& l = net.lb[i];
-      long long Min = pl.lbe[i].M, Mout = pl.lbd[i].M;
-      int Ho = i < 3 ? pl.H4 : pl.H5, Wo = i < 3 ? pl.W4 : pl.W5;
-      pw_slab(Min, l.cin * 6, l.cin);
-      pw_slab(Mout, l.cout, l.cin * 6);
-      dw_slab(Ho, Wo, l.cin * 6, l.stride);
-    }
-    for (int i = 0; i < 4; ++i) pw_slab(pl.ppk[i].M, 32, 128);
-    pw_slab(M5, 128, 256);
-    for (int i = 0; i < 3; ++i) dw_slab(pl.H3, pl.W3, 128, 1);  // FFM dw, classifier dw x2
-    pw_slab(M2, 128, 128, true); pw_slab(M2, 128, 64, true);   // FFM low / high (bias)
-    pw_slab(M2, 128, 128); pw_slab(M2, 128, 128);              // classifier dsconv pw x2
-    pw_slab(M2, C, 128, true);                                 // classifier 1x1 (bias)
-    if (net.aux) { pw_slab(M2, 32, 576); pw_slab(M2, C, 32, true); }
+    for_each_unit(pl, [&](const Unit& u) {
+      if (u.kind == U_PW) pw_slab(*u.conv, u.M);
+      if (u.kind == U_DW)
+        add_slab((size_t)dw_wgrad_parts(N, u.Ho, u.Wo, u.C, dtype, u.stride) * 9 * u.C);
+    });
+    // the convs without a unit (no BN): the classifier's and the aux head's last 1x1
+    pw_slab(net.cls_out, M2);
+    if (net.aux) pw_slab(net.aux4, M2);
+    // conv0's weight gradient: as its own launch, and the fused LTD backward's form
     add_slab((size_t)conv0_wgrad_parts(N, pl.H1, pl.W1, 8) * 864);
-    add_slab((size_t)ltd_c0_bwd_parts(N, pl.H1, pl.W1) * LC0_SLAB);  // (the fused form's)
+    add_slab((size_t)ltd_c0_bwd_parts(N, pl.H1, pl.W1) * LC0_SLAB);
     pl.slab_floats = slab;
     pl.slab = B.get(slab * 4);
     // BN backward partials: max P*2*C
     size_t bnp = 0;
-    auto bn_upd = [&](const Unit& u) {
+    auto bnp_max = [&](size_t s) { if (s > bnp) bnp = s; };
+    for_each_unit(pl, [&](const Unit& u) {
       int rpb;
-      size_t s = (size_t)bn_bwd_parts(u.M, u.C, dtype, &rpb) * 2 * u.C;
-      if (s > bnp) bnp = s;
-      s = (size_t)gemm_parts((int)u.M) * 2 * u.C;  // fused dgrad-epilogue records
-      if (s > bnp) bnp = s;
-    };
-    bn_upd(pl.c0); bn_upd(pl.l1dw); bn_upd(pl.l1pw); bn_upd(pl.l2dw); bn_upd(pl.l2pw);
-    for (int i = 0; i < 9; ++i) { bn_upd(pl.lbe[i]); bn_upd(pl.lbd[i]); bn_upd(pl.lbp[i]); }
-    for (int i = 0; i < 4; ++i) bn_upd(pl.ppk[i]);
-    bn_upd(pl.po); bn_upd(pl.fdw); bn_upd(pl.flow); bn_upd(pl.c1dw); bn_upd(pl.c1pw);
-    if (net.aux) bn_upd(pl.aux0);
-    // depthwise dgrads producing a BN's dy write dw_dgrad_parts records (Executor::dw_bwd)
-    auto dw_upd = [&](int H, int W, int Cc, int stride) {
-      const size_t s = (size_t)dw_dgrad_parts(N, H, W, Cc, dtype, stride) * 2 * Cc;
-      if (s > bnp) bnp = s;
-    };
-    dw_upd(pl.H1, pl.W1, 32, 2); dw_upd(pl.H2, pl.W2, 48, 2);
-    for (int i = 0; i < 9; ++i) {
-      const int Hin = i == 0 ? pl.H3 : (i <= 3 ? pl.H4 : pl.H5);
-      const int Win = i == 0 ? pl.W3 : (i <= 3 ? pl.W4 : pl.W5);
-      dw_upd(Hin, Win, net.lb[i].cin * 6, net.lb[i].stride);
-    }
-    dw_upd(pl.H3, pl.W3, 128, 1);
+      bnp_max((size_t)bn_bwd_parts(u.M, u.C, dtype, &rpb) * 2 * u.C);
+      bnp_max((size_t)gemm_parts((int)u.M) * 2 * u.C);  // fused dgrad-epilogue records
+      // depthwise dgrads producing a BN's dy write dw_dgrad_parts records (Exec::dw_bwd)
+      if (u.kind == U_DW)
+        bnp_max((size_t)dw_dgrad_parts(N, u.Hi, u.Wi, u.C, dtype, u.stride) * 2 * u.C);
+    });
     {  // the FFM pair (Exec::bn_bwd_pair) keeps both BNs' records side by side
       int rpb;
-      const size_t s = (size_t)2 * bn_bwd_parts(pl.flow.M, 128, dtype, &rpb) * 2 * 128;
-      if (s > bnp) bnp = s;
+      bnp_max((size_t)2 * bn_bwd_parts(pl.flow.M, 128, dtype, &rpb) * 2 * 128);
     }
     pl.bnpart = B.get(bnp * 4);
     pl.bnpart_floats = bnp;
@@ -493,17 +454,13 @@ int plan_build(const Net& net, int N, int H, int W, int dtype, int train, Plan& 
     pl.c0sum = B.get((size_t)LC0_SLAB * 4);  // reduced conv0 partials of the fused LTD backward
     pl.cspart = B.get((size_t)colsum_parts((int)M2) * (C > 128 ? C : 128) * 4);
     pl.bws_bytes = B.top;
-    auto gu = [&](const std::string& n, const Unit& u) {
-      pl.named.push_back({n + ".ga", u.ga, u.M, u.C, u.ga_ld, 1});
-    };
-    gu("c0", pl.c0); gu("l1dw", pl.l1dw); gu("l1pw", pl.l1pw); gu("l2dw", pl.l2dw); gu("l2pw", pl.l2pw);
-    for (int i = 0; i < 9; ++i) {
-      gu("lbe" + std::to_string(i), pl.lbe[i]);
-      gu("lbd" + std::to_string(i), pl.lbd[i]);
-      gu("lbp" + std::to_string(i), pl.lbp[i]);
-    }
-    gu("po", pl.po); gu("fdw", pl.fdw); gu("c1dw", pl.c1dw); gu("c1pw", pl.c1pw);
-    gu("c2dw", pl.c2dw); gu("c2pw", pl.c2pw);
+    // (not exposed: the PPM branches' slices of g_feats and the aux head's gradient; the FFM's
+    // two 1x1 branches have no gradient buffer, ga_ld == 0)
+    for_each_unit(pl, [&](const Unit& u) {
+      const bool ppk = &u >= pl.ppk && &u < pl.ppk + 4;
+      if (u.ga_ld && !ppk && &u != &pl.aux0)
+        pl.named.push_back({u.key + ".ga", u.ga, u.M, u.C, u.ga_ld, 1});
+    });
     nm("g_logits", pl.g_logits, M2, C, pl.Cp, 1);
     nm("g_f", pl.g_f, M2, 128, 128, 1);
     nm("g_up", pl.g_up, M2, 128, 128, 1);
@@ -650,7 +607,6 @@ bool drop_dgrad_on() {
 // fused BN-backward partials: the dgrad GEMM producing the dy of unit `u` emits its records
 struct BTarget {
   const Unit* u = nullptr;
-  const BnL* bn = nullptr;
   int mode = 0;  // 0 no ReLU, 2 relu_z (mask recomputed from z)
 };
 
@@ -782,8 +738,7 @@ struct Exec {
     }
     for (int i = 0; i < 9; ++i) {  // fp32 inference: split planes of the fused bottlenecks
       if (!pl.lb_we3[i]) continue;
-      const LbL& l = net.lb[i];
-      const ConvL* cs[2] = {&l.e, &l.p};
+      const ConvL* cs[2] = {pl.lbe[i].conv, pl.lbp[i].conv};
       const size_t offs[2] = {pl.lb_we3[i], pl.lb_wp3[i]};
       for (int k = 0; k < 2; ++k) {
         PrepJob& j = t.j[t.n++];
@@ -797,11 +752,12 @@ struct Exec {
         j.src = c.w; j.dst = (long long)(pl.wt / E) + c.wt; j.R = c.cout;
         j.Cc = c.cin * c.k * c.k; j.ld = c.ldt; j.trans = 1;
       };
-      add(net.ltd1.pw); add(net.ltd2.pw);
-      for (int i = 0; i < 9; ++i) { add(net.lb[i].e); add(net.lb[i].p); }
-      for (int i = 0; i < 4; ++i) add(net.ppm_c[i]);
-      add(net.ppm_o); add(net.ffm_low); add(net.ffm_high);
-      add(net.cls1.pw); add(net.cls2.pw); add(net.cls_out);
+      // every dense conv with a dgrad: the pointwise units', then the classifier's unit-less
+      // 1x1, then the aux head's two (the table's job order is part of the launch)
+      for_each_unit(pl, [&](const Unit& u) {
+        if (u.kind == U_PW && &u != &pl.aux0) add(*u.conv);
+      });
+      add(net.cls_out);
       if (net.aux) { add(net.aux0); add(net.aux4); }
       PrepJob& z = t.j[t.n++];  // BN arrival counters (fcnt, bcnt: 2 x BN_COUNTERS uint32)
       z.src = 0; z.dst = (long long)(pl.fcnt / E); z.R = 1; z.Cc = (int)(2 * BN_COUNTERS * 4 / E);
@@ -853,7 +809,7 @@ struct Exec {
     c0_combine = false;
     g_prof_tag = "learning_to_downsample.conv (weight gradient)";
     return conv0_wgrad_combine((const float*)Bw(pl.c0sum), (const float*)Bw(pl.xtab),
-                               Wf(pl.c0.mean), G(net.c0.w), r.st);
+                               Wf(pl.c0.mean), G(pl.c0.conv->w), r.st);
   }
   int slab_oom() {
     set_error("backward: weight-gradient slab arena exhausted");
@@ -874,7 +830,8 @@ struct Exec {
   static In raw(const void* p, int ld) { return {p, ld, nullptr, nullptr}; }
 
   // ---- BN glue -----------------------------------------------------------------------
-  BnFinalizeArgs fin_args(const Unit& u, const BnL& bn) const {
+  BnFinalizeArgs fin_args(const Unit& u) const {
+    const BnL& bn = *u.bn;
     BnFinalizeArgs f{};
     f.part = Wf(u.part); f.P = u.nparts; f.C = u.C;
     f.gamma = P(bn.g); f.beta = P(bn.b);
@@ -886,15 +843,15 @@ struct Exec {
     f.counters = (unsigned*)W(pl.fcnt);  // one launch (fold + last-arriver finalize)
     return f;
   }
-  int finalize(const Unit& u, const BnL& bn) {
+  int finalize(const Unit& u) {
     g_prof_tag = u.name.c_str();
-    return bn_finalize(fin_args(u, bn), r.st);
+    return bn_finalize(fin_args(u), r.st);
   }
   // a GEMM producer finishes its BN itself (gemm_nt: in-kernel, or its own finalize launch)
-  void gemm_fin(GemmArgs& g, const Unit& u, const BnL& bn) const {
+  void gemm_fin(GemmArgs& g, const Unit& u) const {
     g.part = Wf(u.part);
     g.tail.counters = (unsigned*)W(pl.fcnt);
-    g.tail.fwd = fin_args(u, bn);
+    g.tail.fwd = fin_args(u);
     g.tail.tsum = (double*)W(pl.tsum);
   }
   int apply(const Unit& u, bool relu, const void* res = nullptr, int ldres = 0) {
@@ -909,19 +866,20 @@ struct Exec {
   }
 
   // ---- conv + BN (+ReLU) producers -------------------------------------------------------
-  // pointwise conv on X [M][K] (ld ldx); eval: fused BN(+res,+relu); train: stats → apply
+  // pointwise conv of unit u on X [M][K] (ld ldx); eval: fused BN(+res,+relu); train: stats → apply
   // store_out = false (train): the BN+ReLU output is applied by its only consumer instead
-  int pw(const Unit& u, const ConvL& c, const BnL* bn, In x, bool relu,
-         const void* res = nullptr, int ldres = 0, bool store_out = true) {
+  int pw(const Unit& u, In x, bool relu, const void* res = nullptr, int ldres = 0,
+         bool store_out = true) {
     g_prof_tag = u.name.c_str();
+    const ConvL& c = *u.conv;
     GemmArgs g{};
     const int K = c.cin * c.k * c.k;  // 1x1 convs; the aux 3x3 runs on its im2col columns
     g.M = (int)u.M; g.N = c.cout; g.K = K;
     g.A = x.p; g.lda = x.ld; g.a_scale = x.sc; g.a_shift = x.sh;
     g.B = Wg(c); g.ldb = K; g.b_trans = 0;
-    if (!train || !bn) {
-      g.scale = bn ? Wf(u.scale) : nullptr;
-      g.shift = bn ? Wf(u.shift) : P(c.b);
+    if (!train) {
+      g.scale = Wf(u.scale);
+      g.shift = Wf(u.shift);
       g.R = res; g.ldr = ldres;
       g.relu = relu;
       g.C = W(u.a); g.ldc = u.ld;
@@ -929,16 +887,16 @@ struct Exec {
     }
     g.scale = nullptr; g.shift = P(c.b);
     g.C = W(u.z); g.ldc = u.C;
-    if (!frozen) gemm_fin(g, u, *bn);
+    if (!frozen) gemm_fin(g, u);
     TRY(gemm_nt(g, dt, r.st));
     return (u.lazy || !store_out) ? OK : apply(u, relu, res, ldres);
   }
-  int dw(const Unit& u, const ConvL& c, const BnL& bn, In x, int H, int Wd, int Ho, int Wo,
-         int stride) {
+  // depthwise conv of unit u (its own geometry) on x
+  int dw(const Unit& u, In x) {
     g_prof_tag = u.name.c_str();
     DwArgs d{};
-    d.N = pl.N; d.H = H; d.W = Wd; d.C = u.C; d.Ho = Ho; d.Wo = Wo; d.stride = stride;
-    d.x = x.p; d.w = P(c.w); d.in_scale = x.sc; d.in_shift = x.sh;
+    d.N = pl.N; d.H = u.Hi; d.W = u.Wi; d.C = u.C; d.Ho = u.Ho; d.Wo = u.Wo; d.stride = u.stride;
+    d.x = x.p; d.w = P(u.conv->w); d.in_scale = x.sc; d.in_shift = x.sh;
     if (x.ld != u.C) {
       set_error("dw: strided input (ld %d, C %d) not supported", x.ld, u.C);
       return E_UNSUPPORTED;
@@ -951,7 +909,7 @@ struct Exec {
     if (!frozen) {
       d.part = Wf(u.part);
       d.tail.counters = (unsigned*)W(pl.fcnt);  // dw_fwd finishes the BN (in-kernel when it fits)
-      d.tail.fwd = fin_args(u, bn);
+      d.tail.fwd = fin_args(u);
       d.tail.tsum = (double*)W(pl.tsum);
     }
     TRY(dw_fwd(d, dt, r.st));
@@ -994,30 +952,16 @@ struct Exec {
 
   int fold_all() {
     FoldTable t{};
-    auto add = [&](const BnL& bn, const Unit& u, const ConvL* conv) {
+    for_each_unit(pl, [&](const Unit& u) {
+      const BnL& bn = *u.bn;
       FoldEntry& e = t.e[t.n++];
       e.gamma = P(bn.g); e.beta = P(bn.b); e.rmean = r.R + bn.rm; e.rvar = r.R + bn.rv;
+      // the conv's bias, where it has one (the FFM's 1x1 branches), folds into the shift
       // (frozen: the stored z already carries the conv bias, as in training plans)
-      e.bias = (!frozen && conv && conv->b >= 0) ? P(conv->b) : nullptr;
+      e.bias = (!frozen && u.conv->b >= 0) ? P(u.conv->b) : nullptr;
       e.scale = Wf(u.scale); e.shift = Wf(u.shift); e.C = bn.C;
       if (frozen) { e.mean = Wf(u.mean); e.invstd = Wf(u.invstd); }
-    };
-    add(net.b0, pl.c0, nullptr);
-    add(net.ltd1.bdw, pl.l1dw, nullptr); add(net.ltd1.bpw, pl.l1pw, nullptr);
-    add(net.ltd2.bdw, pl.l2dw, nullptr); add(net.ltd2.bpw, pl.l2pw, nullptr);
-    for (int i = 0; i < 9; ++i) {
-      add(net.lb[i].be, pl.lbe[i], nullptr);
-      add(net.lb[i].bd, pl.lbd[i], nullptr);
-      add(net.lb[i].bp, pl.lbp[i], nullptr);
-    }
-    for (int i = 0; i < 4; ++i) add(net.ppm_b[i], pl.ppk[i], nullptr);
-    add(net.ppm_ob, pl.po, nullptr);
-    add(net.ffm_bdw, pl.fdw, nullptr);
-    add(net.ffm_blow, pl.flow, &net.ffm_low);
-    add(net.ffm_bhigh, pl.fhigh, &net.ffm_high);
-    add(net.cls1.bdw, pl.c1dw, nullptr); add(net.cls1.bpw, pl.c1pw, nullptr);
-    add(net.cls2.bdw, pl.c2dw, nullptr); add(net.cls2.bpw, pl.c2pw, nullptr);
-    if (net.aux) add(net.aux1, pl.aux0, nullptr);
+    });
     return bn_fold(t, r.st);
   }
 
@@ -1033,9 +977,9 @@ struct Exec {
     if (!train) {  // inference: conv + dsconv1 (dw, pw) in one launch (stem.hip) when it fits
       sa.x = r.x; sa.x_dtype = r.x_dtype;
       sa.N = N; sa.H = pl.H; sa.W = pl.W; sa.H1 = pl.H1; sa.W1 = pl.W1; sa.H2 = pl.H2; sa.W2 = pl.W2;
-      sa.w0 = P(net.c0.w); sa.sc0 = Wf(pl.c0.scale); sa.sh0 = Wf(pl.c0.shift);
-      sa.wd = P(net.ltd1.dw.w); sa.scd = Wf(pl.l1dw.scale); sa.shd = Wf(pl.l1dw.shift);
-      sa.wp = Wg(net.ltd1.pw); sa.scp = Wf(pl.l1pw.scale); sa.shp = Wf(pl.l1pw.shift);
+      sa.w0 = P(pl.c0.conv->w); sa.sc0 = Wf(pl.c0.scale); sa.sh0 = Wf(pl.c0.shift);
+      sa.wd = P(pl.l1dw.conv->w); sa.scd = Wf(pl.l1dw.scale); sa.shd = Wf(pl.l1dw.shift);
+      sa.wp = Wg(*pl.l1pw.conv); sa.scp = Wf(pl.l1pw.scale); sa.shp = Wf(pl.l1pw.shift);
       sa.y = W(pl.l1pw.a); sa.ldy = pl.l1pw.ld;
     }
     if (!train && stem_enabled() && stem_ok(sa)) {
@@ -1045,16 +989,16 @@ struct Exec {
       Conv0Args c{};
       c.x = r.x; c.x_bf16 = r.x_dtype;
       c.N = N; c.H = pl.H; c.W = pl.W; c.Ho = pl.H1; c.Wo = pl.W1;
-      c.w = P(net.c0.w);
+      c.w = P(pl.c0.conv->w);
       if (!train) { c.scale = Wf(pl.c0.scale); c.shift = Wf(pl.c0.shift); c.relu = 1; c.y = W(pl.c0.a); }
       else { c.relu = 0; c.y = W(pl.c0.z); c.part = frozen ? nullptr : Wf(pl.c0.part); }
       TRY(conv0_fwd(c, dt, r.st));
       if (train) {
-        if (!frozen) TRY(finalize(pl.c0, net.b0));
+        if (!frozen) TRY(finalize(pl.c0));
         if (!pl.c0.lazy) TRY(apply(pl.c0, true));
       }
-      TRY(dw(pl.l1dw, net.ltd1.dw, net.ltd1.bdw, act(pl.c0), pl.H1, pl.W1, pl.H2, pl.W2, 2));
-      TRY(pw(pl.l1pw, net.ltd1.pw, &net.ltd1.bpw, act(pl.l1dw), true));
+      TRY(dw(pl.l1dw, act(pl.c0)));
+      TRY(pw(pl.l1pw, act(pl.l1dw), true));
     }
     {
       // inference: dsconv2's depthwise s2 + pointwise in one launch (dsconv.hip ds2_fwd), its
@@ -1062,15 +1006,15 @@ struct Exec {
       Ds2Args d2{};
       const In xin = act(pl.l1pw);
       d2.x = xin.p; d2.N = N; d2.H = pl.H2; d2.W = pl.W2; d2.Ho = pl.H3; d2.Wo = pl.W3;
-      d2.wd = P(net.ltd2.dw.w); d2.scd = Wf(pl.l2dw.scale); d2.shd = Wf(pl.l2dw.shift);
-      d2.wp = Wg(net.ltd2.pw); d2.scp = Wf(pl.l2pw.scale); d2.shp = Wf(pl.l2pw.shift);
+      d2.wd = P(pl.l2dw.conv->w); d2.scd = Wf(pl.l2dw.scale); d2.shd = Wf(pl.l2dw.shift);
+      d2.wp = Wg(*pl.l2pw.conv); d2.scp = Wf(pl.l2pw.scale); d2.shp = Wf(pl.l2pw.shift);
       d2.y = W(pl.l2pw.a); d2.ldy = pl.l2pw.ld;
       if (!train && ltd2_enabled() && !xin.sc && xin.ld == 48 && ds2_ok(d2)) {
         g_prof_tag = "learning_to_downsample.dsconv2 (dw + pw, fused)";
         TRY(ds2_fwd(d2, dt, r.st));
       } else {
-        TRY(dw(pl.l2dw, net.ltd2.dw, net.ltd2.bdw, xin, pl.H2, pl.W2, pl.H3, pl.W3, 2));
-        TRY(pw(pl.l2pw, net.ltd2.pw, &net.ltd2.bpw, act(pl.l2dw), true));
+        TRY(dw(pl.l2dw, xin));
+        TRY(pw(pl.l2pw, act(pl.l2dw), true));
       }
     }
     // train: the FeatureFusionModule's high-res branch (conv_higher_res + its BN statistics, on
@@ -1093,20 +1037,18 @@ struct Exec {
     // ---- bottlenecks ----
     const void* x = W(pl.l2pw.a);
     int xld = 64;
-    int Hc = pl.H3, Wc = pl.W3;
     for (int i = 0; i < 9; ++i) {
       if (fhigh_side && i == pack_at) {
         TRY(side_launch([this](hipStream_t s) { return pack_targets(s); }));
         TRY(flush_side());
       }
       const LbL& l = net.lb[i];
-      int Ho = dwout(Hc, l.stride), Wo = dwout(Wc, l.stride);
       IrArgs b;
-      if (ir_block_shape(net, pl, i, b)) {
+      if (ir_block_shape(pl, i, b)) {
         // inference: the whole stride-1 block in one launch (ir.hip), the 6x-expanded tensor
         // never leaves LDS
         b.x = x; b.ldx = xld; b.y = W(pl.lbp[i].a);
-        b.we = Wg(l.e); b.wd = P(l.d.w); b.wp = Wg(l.p);
+        b.we = Wg(*pl.lbe[i].conv); b.wd = P(pl.lbd[i].conv->w); b.wp = Wg(*pl.lbp[i].conv);
         b.sc_e = Wf(pl.lbe[i].scale); b.sh_e = Wf(pl.lbe[i].shift);
         b.sc_d = Wf(pl.lbd[i].scale); b.sh_d = Wf(pl.lbd[i].shift);
         b.sc_p = Wf(pl.lbp[i].scale); b.sh_p = Wf(pl.lbp[i].shift);
@@ -1118,17 +1060,14 @@ struct Exec {
         TRY(ir_block_fwd(b, dt, r.st));
         x = W(pl.lbp[i].a);
         xld = pl.lbp[i].ld;
-        Hc = Ho; Wc = Wo;
         continue;
       }
-      TRY(pw(pl.lbe[i], l.e, &l.be, i == 0 ? act(pl.l2pw) : raw(x, xld), true));
-      TRY(dw(pl.lbd[i], l.d, l.bd, act(pl.lbe[i]), Hc, Wc, Ho, Wo, l.stride));
+      TRY(pw(pl.lbe[i], i == 0 ? act(pl.l2pw) : raw(x, xld), true));
+      TRY(dw(pl.lbd[i], act(pl.lbe[i])));
       bool shortcut = l.stride == 1 && l.cin == l.cout;
-      TRY(pw(pl.lbp[i], l.p, &l.bp, act(pl.lbd[i]), false, shortcut ? x : nullptr,
-             shortcut ? xld : 0));
+      TRY(pw(pl.lbp[i], act(pl.lbd[i]), false, shortcut ? x : nullptr, shortcut ? xld : 0));
       x = W(pl.lbp[i].a);
       xld = pl.lbp[i].ld;
-      Hc = Ho; Wc = Wo;
     }
     // ---- PPM ----
     {
@@ -1137,7 +1076,6 @@ struct Exec {
       p.N = N; p.H = pl.H5; p.W = pl.W5; p.C = 128; p.x = W(pl.concat); p.ldx = 256;
       p.pooled = W(pl.pooled);
       TRY(pyramid_pool(p, dt, r.st));
-      static const int base[4] = {0, 1, 5, 14};
       if (ppm_fused()) {
         // the four branch convs + BN + ReLU in one launch (block-local batch statistics)
         g_prof_tag = "global_feature_extractor.ppm.conv1-4";
@@ -1146,9 +1084,9 @@ struct Exec {
         for (int i = 0; i < 4; ++i) {
           const Unit& u = pl.ppk[i];
           PpmBranchFwd& b = f.b[i];
-          b.f = fin_args(u, net.ppm_b[i]);
-          b.x = (char*)W(pl.pooled) + (size_t)base[i] * N * 128 * E;
-          b.w = Wg(net.ppm_c[i]);
+          b.f = fin_args(u);
+          b.x = (char*)W(pl.pooled) + (size_t)PPM_BASE[i] * N * 128 * E;
+          b.w = Wg(*u.conv);
           b.z = W(u.z); b.y = W(u.a); b.ldy = u.ld; b.M = (int)u.M;
         }
         TRY(ppm_branches_fwd(f, dt, r.st));
@@ -1162,15 +1100,15 @@ struct Exec {
           const Unit& u = pl.ppk[i];
           PpmBranchFwd& b = f.b[i];
           b.f.scale = Wf(u.scale); b.f.shift = Wf(u.shift);
-          b.x = (char*)W(pl.pooled) + (size_t)base[i] * N * 128 * E;
-          b.w = Wg(net.ppm_c[i]);
+          b.x = (char*)W(pl.pooled) + (size_t)PPM_BASE[i] * N * 128 * E;
+          b.w = Wg(*u.conv);
           b.y = W(u.a); b.ldy = u.ld; b.M = (int)u.M;
         }
         TRY(ppm_branches_fwd(f, dt, r.st));
       } else {
         for (int i = 0; i < 4; ++i) {
-          const void* xin = (char*)W(pl.pooled) + (size_t)base[i] * N * 128 * E;
-          TRY(pw(pl.ppk[i], net.ppm_c[i], &net.ppm_b[i], raw(xin, 128), true));
+          const void* xin = (char*)W(pl.pooled) + (size_t)PPM_BASE[i] * N * 128 * E;
+          TRY(pw(pl.ppk[i], raw(xin, 128), true));
         }
       }
       g_prof_tag = "global_feature_extractor.ppm.upsample";
@@ -1178,7 +1116,7 @@ struct Exec {
       u.N = N; u.H = pl.H5; u.W = pl.W5; u.CF = 32; u.feats = W(pl.feats_a);
       u.y = W(pl.concat); u.ldy = 256; u.coff = 128;
       TRY(ppm_up_fwd(u, dt, r.st));
-      TRY(pw(pl.po, net.ppm_o, &net.ppm_ob, raw(W(pl.concat), 256), true));
+      TRY(pw(pl.po, raw(W(pl.concat), 256), true));
     }
     // ---- FFM ----
     {
@@ -1192,17 +1130,17 @@ struct Exec {
         DsArgs fa{};  // the upsample too: the depthwise reads the PPM output through it
         fa.x = W(pl.po.a); fa.Hi = pl.H5; fa.Wi = pl.W5;
         fa.N = N; fa.H = pl.H3; fa.W = pl.W3; fa.C = 128; fa.Co = 128;
-        fa.wd = P(net.ffm_dw.w); fa.scd = Wf(pl.fdw.scale); fa.shd = Wf(pl.fdw.shift);
-        fa.wp = Wg(net.ffm_low); fa.scp = Wf(pl.flow.scale); fa.shp = Wf(pl.flow.shift);
+        fa.wd = P(pl.fdw.conv->w); fa.scd = Wf(pl.fdw.scale); fa.shd = Wf(pl.fdw.shift);
+        fa.wp = Wg(*pl.flow.conv); fa.scp = Wf(pl.flow.scale); fa.shp = Wf(pl.flow.shift);
         fa.y = W(pl.flow.a); fa.ldy = pl.flow.ld;
         fa.rs = ds_rows(N, pl.H3, pl.W3);
         // and the high-res branch (conv_higher_res + BN) as a second GEMM in the same launch
         DsArgs fh = fa;
-        fh.xh = W(pl.l2pw.a); fh.ldxh = 64; fh.wh = Wg(net.ffm_high);
+        fh.xh = W(pl.l2pw.a); fh.ldxh = 64; fh.wh = Wg(*pl.fhigh.conv);
         fh.sch = Wf(pl.fhigh.scale); fh.shh = Wf(pl.fhigh.shift);
         fa.r = W(pl.f); fa.ldr = 128;
         const bool hi_fused = ds_enabled() && ffm_hi_enabled() && ds_ok(fh);
-        if (!hi_fused) TRY(pw(pl.fhigh, net.ffm_high, &net.ffm_bhigh, raw(W(pl.l2pw.a), 64), false));
+        if (!hi_fused) TRY(pw(pl.fhigh, raw(W(pl.l2pw.a), 64), false));
         if (hi_fused) {
           g_prof_tag = "feature_fusion (upsample + dwconv + conv_lower_res + conv_higher_res, fused)";
           TRY(ds_fwd(fh, dt, r.st));
@@ -1212,20 +1150,20 @@ struct Exec {
         } else {
           g_prof_tag = "feature_fusion.upsample";
           TRY(up_nhwc(u, dt, r.st));
-          TRY(dw(pl.fdw, net.ffm_dw, net.ffm_bdw, raw(W(pl.up_low), 128), pl.H3, pl.W3, pl.H3, pl.W3, 1));
-          TRY(pw(pl.flow, net.ffm_low, &net.ffm_blow, act(pl.fdw), true, W(pl.f), 128));
+          TRY(dw(pl.fdw, raw(W(pl.up_low), 128)));
+          TRY(pw(pl.flow, act(pl.fdw), true, W(pl.f), 128));
         }
       } else {
         TRY(up_nhwc(u, dt, r.st));
-        TRY(dw(pl.fdw, net.ffm_dw, net.ffm_bdw, raw(W(pl.up_low), 128), pl.H3, pl.W3, pl.H3, pl.W3, 1));
+        TRY(dw(pl.fdw, raw(W(pl.up_low), 128)));
         g_prof_tag = pl.flow.name.c_str();
         GemmArgs g{};
         const In fin = act(pl.fdw);
         g.M = (int)pl.flow.M; g.N = 128; g.K = 128; g.A = fin.p; g.lda = fin.ld;
         g.a_scale = fin.sc; g.a_shift = fin.sh;
-        g.B = Wg(net.ffm_low); g.ldb = 128; g.shift = P(net.ffm_low.b);
+        g.B = Wg(*pl.flow.conv); g.ldb = 128; g.shift = P(pl.flow.conv->b);
         g.C = W(pl.flow.z); g.ldc = 128;
-        if (!frozen) gemm_fin(g, pl.flow, net.ffm_blow);
+        if (!frozen) gemm_fin(g, pl.flow);
         TRY(gemm_nt(g, dt, r.st));
         if (fhigh_side) TRY(join());
         else TRY(fhigh_fwd(false));
@@ -1239,29 +1177,29 @@ struct Exec {
     }
     // ---- Classifier ----
     // inference: each DSConv (dw + BN + ReLU, pw + BN + ReLU) in one launch (dsconv.hip)
-    auto ds_args = [&](const DsL& d, const Unit& udw, const Unit& upw, const void* xin) {
+    auto ds_args = [&](const Unit& udw, const Unit& upw, const void* xin) {
       DsArgs s{};
       s.x = xin; s.N = N; s.H = pl.H3; s.W = pl.W3; s.C = 128; s.Co = 128;
-      s.wd = P(d.dw.w); s.scd = Wf(udw.scale); s.shd = Wf(udw.shift);
-      s.wp = Wg(d.pw); s.scp = Wf(upw.scale); s.shp = Wf(upw.shift);
+      s.wd = P(udw.conv->w); s.scd = Wf(udw.scale); s.shd = Wf(udw.shift);
+      s.wp = Wg(*upw.conv); s.scp = Wf(upw.scale); s.shp = Wf(upw.shift);
       s.y = W(upw.a); s.ldy = upw.ld; s.rs = ds_rows(N, pl.H3, pl.W3);
       return s;
     };
     const bool ds_fuse = !train && ds_enabled() && pl.c1pw.ld == 128;
-    const DsArgs ds1 = ds_fuse ? ds_args(net.cls1, pl.c1dw, pl.c1pw, W(pl.f)) : DsArgs{};
+    const DsArgs ds1 = ds_fuse ? ds_args(pl.c1dw, pl.c1pw, W(pl.f)) : DsArgs{};
     if (ds_fuse && ds_ok(ds1)) {
       g_prof_tag = "classifier.dsconv1 (fused)";
       TRY(ds_fwd(ds1, dt, r.st));
     } else {
-      TRY(dw(pl.c1dw, net.cls1.dw, net.cls1.bdw, raw(W(pl.f), 128), pl.H3, pl.W3, pl.H3, pl.W3, 1));
-      TRY(pw(pl.c1pw, net.cls1.pw, &net.cls1.bpw, act(pl.c1dw), true));
+      TRY(dw(pl.c1dw, raw(W(pl.f), 128)));
+      TRY(pw(pl.c1pw, act(pl.c1dw), true));
     }
     // train with Dropout: the dsconv2 pw BN+ReLU output is only read by the dropout, which
     // applies the BN itself (c2pw.a is never stored: one 128-channel write + read fewer)
     const bool drop_fused = train && r.dropout_p > 0.f;
     // (inference: the classifier conv rides in the same launch -- Dropout is the identity -- and
     // the dsconv2 output is never stored)
-    DsArgs ds2 = ds_fuse ? ds_args(net.cls2, pl.c2dw, pl.c2pw, W(pl.c1pw.a)) : DsArgs{};
+    DsArgs ds2 = ds_fuse ? ds_args(pl.c2dw, pl.c2pw, W(pl.c1pw.a)) : DsArgs{};
     if (ds_fuse) {
       ds2.wc = Wg(net.cls_out); ds2.bc = P(net.cls_out.b); ds2.ncls = net.num_classes;
       ds2.logits = W(pl.logits); ds2.ldl = pl.Cp;
@@ -1271,8 +1209,8 @@ struct Exec {
       g_prof_tag = "classifier.dsconv2 + conv (fused)";
       TRY(ds_fwd(ds2, dt, r.st));
     } else {
-      TRY(dw(pl.c2dw, net.cls2.dw, net.cls2.bdw, act(pl.c1pw), pl.H3, pl.W3, pl.H3, pl.W3, 1));
-      TRY(pw(pl.c2pw, net.cls2.pw, &net.cls2.bpw, act(pl.c2dw), true, nullptr, 0, !drop_fused));
+      TRY(dw(pl.c2dw, act(pl.c1pw)));
+      TRY(pw(pl.c2pw, act(pl.c2dw), true, nullptr, 0, !drop_fused));
     }
     const void* cls_in = W(pl.c2pw.a);
     if (drop_fused) {
@@ -1375,9 +1313,9 @@ struct Exec {
     const In hin = act(pl.l2pw);
     g.M = (int)pl.fhigh.M; g.N = 128; g.K = 64; g.A = hin.p; g.lda = hin.ld;
     g.a_scale = hin.sc; g.a_shift = hin.sh;
-    g.B = Wg(net.ffm_high); g.ldb = 64; g.shift = P(net.ffm_high.b);
+    g.B = Wg(*pl.fhigh.conv); g.ldb = 64; g.shift = P(pl.fhigh.conv->b);
     g.C = W(pl.fhigh.z); g.ldc = 128;
-    if (!frozen) gemm_fin(g, pl.fhigh, net.ffm_bhigh);
+    if (!frozen) gemm_fin(g, pl.fhigh);
     if (!on_side) return gemm_nt(g, dt, r.st);
     if (!frozen) {
       g.tail.counters = (unsigned*)W(pl.bcnt);
@@ -1395,7 +1333,7 @@ struct Exec {
     ic.N = pl.N; ic.H = pl.H3; ic.W = pl.W3; ic.C = 64; ic.x = W(pl.l2pw.a); ic.ldx = 64;
     ic.col = W(pl.aux_col); ic.ldcol = 576;
     TRY(im2col3(ic, dt, r.st));
-    TRY(pw(u, net.aux0, &net.aux1, raw(W(pl.aux_col), 576), true));
+    TRY(pw(u, raw(W(pl.aux_col), 576), true));
     const void* ain = W(u.a);
     if (train && r.dropout_p > 0.f) {  // Dropout(0.1): the classifier's mask law with seed + 1
       DropArgs d{};
@@ -1461,8 +1399,8 @@ struct Exec {
       TRY(dropout(d, dt, r.st));
     }
     Dz d;
-    TRY(bn_bwd_x(u, net.aux1, Bw(u.ga), 32, true, dz_buf(u), d));
-    TRY(pw_bwd(net.aux0, u.M, d, raw(W(pl.aux_col), 576), Bw(pl.aux_dcol), 576));
+    TRY(bn_bwd_x(u, Bw(u.ga), 32, true, dz_buf(u), d));
+    TRY(pw_bwd(u, d, raw(W(pl.aux_col), 576), Bw(pl.aux_dcol), 576));
     Col2ImArgs cc{};
     cc.N = N; cc.H = pl.H3; cc.W = pl.W3; cc.C = 64; cc.dcol = Bw(pl.aux_dcol); cc.ldcol = 576;
     cc.dx = Bw(pl.l2pw.ga); cc.lddx = 64; cc.accumulate = 1;
@@ -1482,8 +1420,8 @@ struct Exec {
   };
   static Dz plain(const void* p, int ld) { return {p, ld, nullptr, nullptr}; }
   // reduce + finalize of u's BN backward unless its dy producer did both
-  int bn_bwd_stats(const Unit& u, const BnL& bn, const void* dy, int lddy, const void* mask,
-                   int ldmask, bool relu_z, const BnBwdTab& tb) {
+  int bn_bwd_stats(const Unit& u, const void* dy, int lddy, const void* mask, int ldmask,
+                   bool relu_z, const BnBwdTab& tb) {
     if (u.bdone.get()) return OK;
     BnBwdArgs b{};
     b.M = u.M; b.C = u.C;
@@ -1495,7 +1433,7 @@ struct Exec {
     TRY(bn_bwd_reduce(b, dt, r.st));
     int rpb;
     const int P = bn_bwd_parts(u.M, u.C, dt, &rpb);
-    return bn_bwd_finalize((float*)Bw(pl.bnpart), P, u.C, bcount(u), G(bn.g), G(bn.b),
+    return bn_bwd_finalize((float*)Bw(pl.bnpart), P, u.C, bcount(u), G(u.bn->g), G(u.bn->b),
                            (float*)Bw(pl.coef), r.st, (unsigned*)W(pl.bcnt), tb);
   }
   // Where a BN-backward dz is formed: by bn_bwd_apply (materialised), or — `streaming`, only
@@ -1505,27 +1443,27 @@ struct Exec {
   // latency-bound pointwise / depthwise consumers slowed down by more than the apply they replaced
   // (+0.89 ms vs -0.58 ms over 15 BNs), so they read a materialised dz.
   // fused form: reduce + finalize only; the consumer applies it on load
-  int bn_bwd_x(const Unit& u, const BnL& bn, const void* dy, int lddy, bool relu_z, void* dz,
-               Dz& out, bool streaming = false) {
+  int bn_bwd_x(const Unit& u, const void* dy, int lddy, bool relu_z, void* dz, Dz& out,
+               bool streaming = false) {
     g_prof_tag = u.name.c_str();
     if (!train || !streaming) {
-      TRY(bn_bwd(u, bn, dy, lddy, nullptr, 0, dz, relu_z));
+      TRY(bn_bwd(u, dy, lddy, nullptr, 0, dz, relu_z));
       out = plain(dz, u.C);
       return OK;
     }
     const BnBwdTab tb = bwd_tab(u, relu_z, tab_slot(u));  // written by u's dy producer
-    TRY(bn_bwd_stats(u, bn, dy, lddy, nullptr, 0, relu_z, tb));
+    TRY(bn_bwd_stats(u, dy, lddy, nullptr, 0, relu_z, tb));
     out = {dy, lddy, W(u.z), tb.tab};
     return OK;
   }
-  int bn_bwd(const Unit& u, const BnL& bn, const void* dy, int lddy, const void* mask,
-             int ldmask, void* dz, bool relu_z = false) {
+  int bn_bwd(const Unit& u, const void* dy, int lddy, const void* mask, int ldmask, void* dz,
+             bool relu_z = false) {
     g_prof_tag = u.name.c_str();
     if (!dz) {
       set_error("backward: dz arena exhausted (%s)", u.name.c_str());
       return E_INVALID;
     }
-    TRY(bn_bwd_stats(u, bn, dy, lddy, mask, ldmask, relu_z, BnBwdTab()));
+    TRY(bn_bwd_stats(u, dy, lddy, mask, ldmask, relu_z, BnBwdTab()));
     BnBwdArgs b{};
     b.M = u.M; b.C = u.C;
     b.dy = dy; b.lddy = lddy; b.mask = mask; b.ldmask = ldmask;
@@ -1539,8 +1477,8 @@ struct Exec {
   // the FeatureFusionModule's two BNs, f = relu(BN_l(z_l) + BN_h(z_h)) (models/fast_scnn.py
   // :207-218): the same dy (g_f) and ReLU mask (f) for both, so one reduce pass and one apply
   // pass read them once (the reduce's sum of dy_r is shared; the finishes stay per BN)
-  int bn_bwd_pair(const Unit& u1, const BnL& bn1, const Unit& u2, const BnL& bn2, const void* dy,
-                  int lddy, const void* mask, int ldmask, void* dz1, void* dz2) {
+  int bn_bwd_pair(const Unit& u1, const Unit& u2, const void* dy, int lddy, const void* mask,
+                  int ldmask, void* dz1, void* dz2) {
     g_prof_tag = "feature_fusion (BN backward, both branches)";
     int rpb;
     const int P = bn_bwd_parts(u1.M, u1.C, dt, &rpb);
@@ -1560,17 +1498,13 @@ struct Exec {
     TRY(bn_bwd_reduce(b, dt, r.st));
     float* coef = (float*)Bw(pl.coef);
     float* coef2 = coef + 2 * u1.C;
-    TRY(bn_bwd_finalize(b.part, P, u1.C, bcount(u1), G(bn1.g), G(bn1.b), coef, r.st,
+    TRY(bn_bwd_finalize(b.part, P, u1.C, bcount(u1), G(u1.bn->g), G(u1.bn->b), coef, r.st,
                         (unsigned*)W(pl.bcnt), BnBwdTab()));
-    TRY(bn_bwd_finalize(b.part2, P, u2.C, bcount(u2), G(bn2.g), G(bn2.b), coef2, r.st,
+    TRY(bn_bwd_finalize(b.part2, P, u2.C, bcount(u2), G(u2.bn->g), G(u2.bn->b), coef2, r.st,
                         (unsigned*)W(pl.bcnt), BnBwdTab()));
     b.coef = coef; b.coef2 = coef2;
     b.dz = dz1; b.dz2 = dz2; b.lddz = u1.C;
     return bn_bwd_apply(b, dt, r.st);
-  }
-  // BN whose output is relu(BN(z)) with no second branch: the ReLU mask is recomputed from z
-  int bn_bwd_relu(const Unit& u, const BnL& bn, const void* dy, int lddy, void* dz) {
-    return bn_bwd(u, bn, dy, lddy, nullptr, 0, dz, true);
   }
   // the dgrad producing the dy of BN (u, bn) also reduces and finishes that BN's backward
   // (gemm_nt: in-kernel, or its own finalize launch); its bn_bwd then only applies
@@ -1583,8 +1517,8 @@ struct Exec {
     g.tail.counters = (unsigned*)W(pl.bcnt);
     g.tail.tsum = (double*)W(pl.tsum);
     g.tail.count = bcount(u);
-    g.tail.dgamma = G(t.bn->g);
-    g.tail.dbeta = G(t.bn->b);
+    g.tail.dgamma = G(u.bn->g);
+    g.tail.dbeta = G(u.bn->b);
     g.tail.coef = (float*)Bw(pl.coef);
     // the operand table too: a fused consumer (depthwise, or every pointwise one in mode 2)
     // reads it instead of a materialised dz (the target's own slot, see bn_bwd_x)
@@ -1648,24 +1582,30 @@ struct Exec {
     if (bt.u && train) bt.u->bdone.set();
     return OK;
   }
-  static BTarget relu_target(const Unit& u, const BnL& bn) {
-    BTarget t; t.u = &u; t.bn = &bn; t.mode = 2; return t;
+  // ... of unit u's conv
+  int pw_bwd(const Unit& u, Dz dz, In X, void* dX, int lddx, const void* R = nullptr, int ldr = 0,
+             BTarget bt = BTarget(), const DropArgs* dro = nullptr) {
+    return pw_bwd(*u.conv, u.M, dz, X, dX, lddx, R, ldr, bt, dro);
   }
-  static BTarget plain_target(const Unit& u, const BnL& bn) {
-    BTarget t; t.u = &u; t.bn = &bn; t.mode = 0; return t;
+  static BTarget relu_target(const Unit& u) {
+    BTarget t; t.u = &u; t.mode = 2; return t;
   }
-  // dw conv backward given dz [M][C]: wgrad into G, dgrad into dX
+  static BTarget plain_target(const Unit& u) {
+    BTarget t; t.u = &u; t.mode = 0; return t;
+  }
+  // backward of depthwise unit u given dz [M][C]: wgrad into G, dgrad into dX
   // bt: the BN whose dy the dgrad produces — its reduce pass is folded into the dgrad (records
   // in bnpart; that BN's backward then only finalizes and applies)
   // dz: this dw's BN-backward output, materialised or as (dy, z, table) applied on load
-  int dw_bwd(const ConvL& c, int C, Dz dz, In X, int H, int Wd, int Ho, int Wo,
-             int stride, void* dX, BTarget bt = BTarget()) {
+  int dw_bwd(const Unit& ud, Dz dz, In X, void* dX, BTarget bt = BTarget()) {
+    const ConvL& c = *ud.conv;
+    const int C = ud.C, Ho = ud.Ho, Wo = ud.Wo, stride = ud.stride;
     if (dz.ld != C) {
       set_error("dw_bwd: strided dz (ld %d, C %d) not supported", dz.ld, C);
       return E_UNSUPPORTED;
     }
     DwBwdArgs d{};
-    d.N = pl.N; d.H = H; d.W = Wd; d.C = C; d.Ho = Ho; d.Wo = Wo; d.stride = stride;
+    d.N = pl.N; d.H = ud.Hi; d.W = ud.Wi; d.C = C; d.Ho = Ho; d.Wo = Wo; d.stride = stride;
     d.x = X.p; d.x_scale = X.sc; d.x_shift = X.sh; d.dy = dz.p; d.w = P(c.w); d.dx = dX;
     if (dz.tab) {
       set_error("dw_bwd: a fused BN-backward operand is not supported here");
@@ -1695,8 +1635,8 @@ struct Exec {
       d.tail.counters = (unsigned*)W(pl.bcnt);
       d.tail.tsum = (double*)W(pl.tsum);
       d.tail.count = bcount(u);
-      d.tail.dgamma = G(bt.bn->g);
-      d.tail.dbeta = G(bt.bn->b);
+      d.tail.dgamma = G(u.bn->g);
+      d.tail.dbeta = G(u.bn->b);
       d.tail.coef = (float*)Bw(pl.coef);
       d.tail.tab = bwd_tab(u, bt.mode == 2, tab_slot(u));
     }
@@ -1740,7 +1680,7 @@ struct Exec {
     DropArgs dd{};
     dd.N = N; dd.H = pl.H3; dd.W = pl.W3; dd.C = 128; dd.seed = r.seed; dd.p = r.dropout_p;
     dd.seed_ptr = seed_ptr();
-    const BTarget dbt = relu_target(pl.c2pw, net.cls2.bpw);
+    const BTarget dbt = relu_target(pl.c2pw);
     const bool dfuse = drop && train && drop_dgrad_on() &&
                        gemm_stream_ok(pw_dgrad_args(net.cls_out, pl.c2pw.M, plain(Bw(pl.g_logits), pl.Cp),
                                                     Bw(pl.c2pw.ga), 128, nullptr, 0, dbt, &dd),
@@ -1762,18 +1702,15 @@ struct Exec {
     }
     // classifier dsconv2, dsconv1
     Dz d;
-    TRY(bn_bwd_x(pl.c2pw, net.cls2.bpw, Bw(pl.c2pw.ga), 128, true, dz_buf(pl.c2pw), d));
-    TRY(pw_bwd(net.cls2.pw, pl.c2pw.M, d, act(pl.c2dw), Bw(pl.c2dw.ga), 128, nullptr, 0,
-               relu_target(pl.c2dw, net.cls2.bdw)));
-    TRY(bn_bwd_x(pl.c2dw, net.cls2.bdw, Bw(pl.c2dw.ga), 128, true, dz_buf(pl.c2dw), d));
-    TRY(dw_bwd(net.cls2.dw, 128, d, act(pl.c1pw), pl.H3, pl.W3, pl.H3, pl.W3, 1, Bw(pl.c1pw.ga),
-               relu_target(pl.c1pw, net.cls1.bpw)));
+    TRY(bn_bwd_x(pl.c2pw, Bw(pl.c2pw.ga), 128, true, dz_buf(pl.c2pw), d));
+    TRY(pw_bwd(pl.c2pw, d, act(pl.c2dw), Bw(pl.c2dw.ga), 128, nullptr, 0, relu_target(pl.c2dw)));
+    TRY(bn_bwd_x(pl.c2dw, Bw(pl.c2dw.ga), 128, true, dz_buf(pl.c2dw), d));
+    TRY(dw_bwd(pl.c2dw, d, act(pl.c1pw), Bw(pl.c1pw.ga), relu_target(pl.c1pw)));
     TRY(flush_side());
-    TRY(bn_bwd_x(pl.c1pw, net.cls1.bpw, Bw(pl.c1pw.ga), 128, true, dz_buf(pl.c1pw), d));
-    TRY(pw_bwd(net.cls1.pw, pl.c1pw.M, d, act(pl.c1dw), Bw(pl.c1dw.ga), 128, nullptr, 0,
-               relu_target(pl.c1dw, net.cls1.bdw)));
-    TRY(bn_bwd_x(pl.c1dw, net.cls1.bdw, Bw(pl.c1dw.ga), 128, true, dz_buf(pl.c1dw), d));
-    TRY(dw_bwd(net.cls1.dw, 128, d, raw(W(pl.f), 128), pl.H3, pl.W3, pl.H3, pl.W3, 1, Bw(pl.g_f)));
+    TRY(bn_bwd_x(pl.c1pw, Bw(pl.c1pw.ga), 128, true, dz_buf(pl.c1pw), d));
+    TRY(pw_bwd(pl.c1pw, d, act(pl.c1dw), Bw(pl.c1dw.ga), 128, nullptr, 0, relu_target(pl.c1dw)));
+    TRY(bn_bwd_x(pl.c1dw, Bw(pl.c1dw.ga), 128, true, dz_buf(pl.c1dw), d));
+    TRY(dw_bwd(pl.c1dw, d, raw(W(pl.f), 128), Bw(pl.g_f)));
     TRY(flush_side());
     // FFM: f = relu(BN_l(z_l) + BN_h(z_h))
     // (low branch first so the low 1x1 dgrad can hand its BN-backward partials straight to
@@ -1781,15 +1718,13 @@ struct Exec {
     void* zl = dz_buf(pl.flow);
     void* zh = dz_buf(pl.fhigh);
     // both branch BNs in one reduce and one apply (same dy g_f and mask f)
-    TRY(bn_bwd_pair(pl.flow, net.ffm_blow, pl.fhigh, net.ffm_bhigh, Bw(pl.g_f), 128, W(pl.f), 128,
-                    zl, zh));
-    TRY(pw_bwd(net.ffm_low, pl.flow.M, plain(zl, 128), act(pl.fdw), Bw(pl.fdw.ga), 128, nullptr, 0,
-               relu_target(pl.fdw, net.ffm_bdw)));
-    TRY(bn_bwd_x(pl.fdw, net.ffm_bdw, Bw(pl.fdw.ga), 128, true, dz_buf(pl.fdw), d));
-    TRY(dw_bwd(net.ffm_dw, 128, d, raw(W(pl.up_low), 128), pl.H3, pl.W3, pl.H3, pl.W3, 1,
-               Bw(pl.g_up)));
+    TRY(bn_bwd_pair(pl.flow, pl.fhigh, Bw(pl.g_f), 128, W(pl.f), 128, zl, zh));
+    TRY(pw_bwd(pl.flow, plain(zl, 128), act(pl.fdw), Bw(pl.fdw.ga), 128, nullptr, 0,
+               relu_target(pl.fdw)));
+    TRY(bn_bwd_x(pl.fdw, Bw(pl.fdw.ga), 128, true, dz_buf(pl.fdw), d));
+    TRY(dw_bwd(pl.fdw, d, raw(W(pl.up_low), 128), Bw(pl.g_up)));
     TRY(flush_side());
-    TRY(pw_bwd(net.ffm_high, pl.fhigh.M, plain(zh, 128), act(pl.l2pw), Bw(pl.l2pw.ga), 64));
+    TRY(pw_bwd(pl.fhigh, plain(zh, 128), act(pl.l2pw), Bw(pl.l2pw.ga), 64));
     TRY(flush_side());
     if (net.aux) TRY(backward_aux());
     // upsample (x4, ac) backward: W pass then H pass → grad of ppm.out activation
@@ -1809,8 +1744,8 @@ struct Exec {
       TRY(axis_bwd(b, DT_F32, dt, r.st));
     }
     // PPM out 1x1 (256→128) over the concat buffer
-    TRY(bn_bwd_x(pl.po, net.ppm_ob, Bw(pl.po.ga), 128, true, dz_buf(pl.po), d));
-    TRY(pw_bwd(net.ppm_o, pl.po.M, d, raw(W(pl.concat), 256), Bw(pl.g_concat), 256));
+    TRY(bn_bwd_x(pl.po, Bw(pl.po.ga), 128, true, dz_buf(pl.po), d));
+    TRY(pw_bwd(pl.po, d, raw(W(pl.concat), 256), Bw(pl.g_concat), 256));
     TRY(flush_side());
     {
       PpmUpArgs u{};
@@ -1818,24 +1753,23 @@ struct Exec {
       u.y = Bw(pl.g_concat); u.ldy = 256; u.coff = 128;
       g_prof_tag = "global_feature_extractor.ppm.upsample (backward)";
       TRY(ppm_up_bwd(u, Bw(pl.g_feats), dt, r.st));
-      static const int base[4] = {0, 1, 5, 14};
       if (ppm_fused()) {
         g_prof_tag = "global_feature_extractor.ppm.conv1-4 (backward)";
         PpmBwdArgs f{};
         f.nb = 4; f.K = 128; f.C = 32;
         for (int i = 0; i < 4; ++i) {
           const Unit& u4 = pl.ppk[i];
-          const size_t off = (size_t)base[i] * N;
+          const size_t off = (size_t)PPM_BASE[i] * N;
           PpmBranchBwd& b = f.b[i];
           b.dy = (char*)Bw(pl.g_feats) + off * 32 * E; b.lddy = 32;
           b.y = (char*)W(pl.feats_a) + off * 32 * E; b.ldy = 32;
           b.z = W(u4.z);
           b.mean = Wf(u4.mean); b.invstd = Wf(u4.invstd); b.scale = Wf(u4.scale);
-          b.gamma = P(net.ppm_b[i].g);
+          b.gamma = P(u4.bn->g);
           b.x = (char*)W(pl.pooled) + off * 128 * E;
-          b.w = Wg(net.ppm_c[i]);
-          b.dgamma = G(net.ppm_b[i].g); b.dbeta = G(net.ppm_b[i].b);
-          b.dw = G(net.ppm_c[i].w);
+          b.w = Wg(*u4.conv);
+          b.dgamma = G(u4.bn->g); b.dbeta = G(u4.bn->b);
+          b.dw = G(u4.conv->w);
           b.dx = (char*)Bw(pl.g_pooled) + off * 128 * E;
           b.M = (int)u4.M;
         }
@@ -1843,11 +1777,11 @@ struct Exec {
       }
       for (int i = 0; i < 4 && !ppm_fused(); ++i) {
         const Unit& u4 = pl.ppk[i];
-        size_t off = (size_t)base[i] * N;
+        size_t off = (size_t)PPM_BASE[i] * N;
         void* zp = dz_buf(u4);
-        TRY(bn_bwd(u4, net.ppm_b[i], (char*)Bw(pl.g_feats) + off * 32 * E, 32,
+        TRY(bn_bwd(u4, (char*)Bw(pl.g_feats) + off * 32 * E, 32,
                    (char*)W(pl.feats_a) + off * 32 * E, 32, zp));
-        TRY(pw_bwd(net.ppm_c[i], u4.M, plain(zp, 32), raw((char*)W(pl.pooled) + off * 128 * E, 128),
+        TRY(pw_bwd(u4, plain(zp, 32), raw((char*)W(pl.pooled) + off * 128 * E, 128),
                    (char*)Bw(pl.g_pooled) + off * 128 * E, 128));
       }
       PoolBwdArgs p{};
@@ -1862,30 +1796,26 @@ struct Exec {
   int backward_block(int i) {
     const LbL& l = net.lb[i];
     const Unit &ue = pl.lbe[i], &ud = pl.lbd[i], &up = pl.lbp[i];
-    int Hin = i == 0 ? pl.H3 : (i <= 3 ? pl.H4 : pl.H5);
-    int Win = i == 0 ? pl.W3 : (i <= 3 ? pl.W4 : pl.W5);
-    int Ho = i < 3 ? pl.H4 : pl.H5, Wo = i < 3 ? pl.W4 : pl.W5;
     const void* x = i == 0 ? W(pl.l2pw.a) : W(pl.lbp[i - 1].a);
     int xld = i == 0 ? 64 : pl.lbp[i - 1].ld;
     void* gx = i == 0 ? Bw(pl.l2pw.ga) : Bw(pl.lbp[i - 1].ga);
     int gxld = i == 0 ? 64 : pl.lbp[i - 1].ga_ld;
     bool shortcut = l.stride == 1 && l.cin == l.cout;
-    const int e = l.cin * 6;
+    const int e = ud.C;
     // up's dy was produced by block i+1's expand dgrad with fused partials (not for the last
     // block: its dy is the PPM concat gradient)
     Dz d;
-    TRY(bn_bwd_x(up, l.bp, Bw(up.ga), up.ga_ld, false, dz_buf(up), d));
-    TRY(pw_bwd(l.p, up.M, d, act(ud), Bw(ud.ga), e, nullptr, 0, relu_target(ud, l.bd)));
-    TRY(bn_bwd_x(ud, l.bd, Bw(ud.ga), e, true, dz_buf(ud), d));
-    TRY(dw_bwd(l.d, e, d, act(ue), Hin, Win, Ho, Wo, l.stride, Bw(ue.ga), relu_target(ue, l.be)));
-    TRY(bn_bwd_x(ue, l.be, Bw(ue.ga), e, true, dz_buf(ue), d));
+    TRY(bn_bwd_x(up, Bw(up.ga), up.ga_ld, false, dz_buf(up), d));
+    TRY(pw_bwd(up, d, act(ud), Bw(ud.ga), e, nullptr, 0, relu_target(ud)));
+    TRY(bn_bwd_x(ud, Bw(ud.ga), e, true, dz_buf(ud), d));
+    TRY(dw_bwd(ud, d, act(ue), Bw(ue.ga), relu_target(ue)));
+    TRY(bn_bwd_x(ue, Bw(ue.ga), e, true, dz_buf(ue), d));
     // grad wrt x: dgrad (+ identity path of the shortcut, or + FFM's contribution for hr)
     const void* R = shortcut ? Bw(up.ga) : (i == 0 ? gx : nullptr);
     int ldr = shortcut ? up.ga_ld : (i == 0 ? gxld : 0);
     // the dgrad is the dy of the previous block's project BN (or of LTD.dsconv2's pw BN)
-    const BTarget bt = i == 0 ? relu_target(pl.l2pw, net.ltd2.bpw)
-                              : plain_target(pl.lbp[i - 1], net.lb[i - 1].bp);
-    TRY(pw_bwd(l.e, ue.M, d, i == 0 ? act(pl.l2pw) : raw(x, xld), gx, gxld, R, ldr, bt));
+    const BTarget bt = i == 0 ? relu_target(pl.l2pw) : plain_target(pl.lbp[i - 1]);
+    TRY(pw_bwd(ue, d, i == 0 ? act(pl.l2pw) : raw(x, xld), gx, gxld, R, ldr, bt));
     return flush_side();  // the block's three wgrads behind one fork
   }
 
@@ -1896,7 +1826,7 @@ struct Exec {
     const Unit& u = pl.c0;
     LtdC0BwdArgs f{};
     f.N = pl.N; f.H = pl.H1; f.W = pl.W1; f.Ho = pl.H2; f.Wo = pl.W2;
-    f.dy = d.p; f.w = P(net.ltd1.dw.w);
+    f.dy = d.p; f.w = P(pl.l1dw.conv->w);
     f.bs.part = (float*)Bw(pl.bnpart);
     f.bs.z = W(u.z);
     f.bs.mean = Wf(u.mean); f.bs.invstd = Wf(u.invstd);
@@ -1905,8 +1835,8 @@ struct Exec {
     f.tail.counters = (unsigned*)W(pl.bcnt);
     f.tail.tsum = (double*)W(pl.tsum);
     f.tail.count = bcount(u);
-    f.tail.dgamma = G(net.b0.g);
-    f.tail.dbeta = G(net.b0.b);
+    f.tail.dgamma = G(u.bn->g);
+    f.tail.dbeta = G(u.bn->b);
     f.tail.coef = (float*)Bw(pl.coef);
     f.tail.tab = bwd_tab(u, true, tab_slot(u));
     f.x = r.x; f.x_dtype = r.x_dtype; f.XH = pl.H; f.XW = pl.W;
@@ -1922,34 +1852,30 @@ struct Exec {
 
   int backward_ltd() {
     Dz d;
-    TRY(bn_bwd_x(pl.l2pw, net.ltd2.bpw, Bw(pl.l2pw.ga), 64, true, dz_buf(pl.l2pw), d));
-    TRY(pw_bwd(net.ltd2.pw, pl.l2pw.M, d, act(pl.l2dw), Bw(pl.l2dw.ga), 48, nullptr, 0,
-               relu_target(pl.l2dw, net.ltd2.bdw)));
-    TRY(bn_bwd_x(pl.l2dw, net.ltd2.bdw, Bw(pl.l2dw.ga), 48, true, dz_buf(pl.l2dw), d));
-    TRY(dw_bwd(net.ltd2.dw, 48, d, act(pl.l1pw), pl.H2, pl.W2, pl.H3, pl.W3, 2, Bw(pl.l1pw.ga),
-               relu_target(pl.l1pw, net.ltd1.bpw)));
+    TRY(bn_bwd_x(pl.l2pw, Bw(pl.l2pw.ga), 64, true, dz_buf(pl.l2pw), d));
+    TRY(pw_bwd(pl.l2pw, d, act(pl.l2dw), Bw(pl.l2dw.ga), 48, nullptr, 0, relu_target(pl.l2dw)));
+    TRY(bn_bwd_x(pl.l2dw, Bw(pl.l2dw.ga), 48, true, dz_buf(pl.l2dw), d));
+    TRY(dw_bwd(pl.l2dw, d, act(pl.l1pw), Bw(pl.l1pw.ga), relu_target(pl.l1pw)));
     TRY(flush_side());
-    TRY(bn_bwd_x(pl.l1pw, net.ltd1.bpw, Bw(pl.l1pw.ga), 48, true, dz_buf(pl.l1pw), d));
-    TRY(pw_bwd(net.ltd1.pw, pl.l1pw.M, d, act(pl.l1dw), Bw(pl.l1dw.ga), 32, nullptr, 0,
-               relu_target(pl.l1dw, net.ltd1.bdw)));
-    TRY(bn_bwd_x(pl.l1dw, net.ltd1.bdw, Bw(pl.l1dw.ga), 32, true, dz_buf(pl.l1dw), d));
+    TRY(bn_bwd_x(pl.l1pw, Bw(pl.l1pw.ga), 48, true, dz_buf(pl.l1pw), d));
+    TRY(pw_bwd(pl.l1pw, d, act(pl.l1dw), Bw(pl.l1dw.ga), 32, nullptr, 0, relu_target(pl.l1dw)));
+    TRY(bn_bwd_x(pl.l1dw, Bw(pl.l1dw.ga), 32, true, dz_buf(pl.l1dw), d));
     // the fused pass never forms conv0's dz, which the input gradient needs
     const bool want_dx = r.dx != nullptr;
     if (!want_dx && ltd_fused_enabled() && ltd_c0_bwd_ok(dt, r.x_dtype, pl.W, r.x)) {
       // (LTD.dsconv1.dw's weight gradient runs beside the fused pass at the side stream's low
       // priority; a normal-priority stream for it alone measured r05 5.888 vs 5.823 ms per step)
-      TRY(dw_bwd(net.ltd1.dw, 32, d, act(pl.c0), pl.H1, pl.W1, pl.H2, pl.W2, 2, nullptr));
+      TRY(dw_bwd(pl.l1dw, d, act(pl.c0), nullptr));
       TRY(ltd1_c0_bwd(d));
       return flush_side();
     }
-    TRY(dw_bwd(net.ltd1.dw, 32, d, act(pl.c0), pl.H1, pl.W1, pl.H2, pl.W2, 2, Bw(pl.c0.ga),
-               relu_target(pl.c0, net.b0)));
+    TRY(dw_bwd(pl.l1dw, d, act(pl.c0), Bw(pl.c0.ga), relu_target(pl.c0)));
     TRY(flush_side());
-    TRY(bn_bwd_x(pl.c0, net.b0, Bw(pl.c0.ga), 32, true, dz_buf(pl.c0), d, !want_dx));
+    TRY(bn_bwd_x(pl.c0, Bw(pl.c0.ga), 32, true, dz_buf(pl.c0), d, !want_dx));
     if (want_dx) {  // d is conv0's materialised dz
       g_prof_tag = "learning_to_downsample.conv (input gradient)";
       Conv0DgradArgs c{};
-      c.dz = d.p; c.w = P(net.c0.w);
+      c.dz = d.p; c.w = P(pl.c0.conv->w);
       c.N = pl.N; c.H = pl.H; c.W = pl.W; c.Ho = pl.H1; c.Wo = pl.W1;
       c.dx = r.dx; c.dx_dtype = r.dx_dtype;
       TRY(conv0_dgrad(c, dt, r.st));
@@ -1963,7 +1889,7 @@ struct Exec {
     if (!c.slab) return slab_oom();
     const int dtc = dt;
     TRY(side_launch([c, dtc](hipStream_t s) { return conv0_wgrad(c, dtc, s); }));
-    TRY(defer_reduce(c.slab, S, 864, G(net.c0.w), 0));
+    TRY(defer_reduce(c.slab, S, 864, G(pl.c0.conv->w), 0));
     return flush_side();
   }
 };

@@ -59,8 +59,17 @@ struct Net {
 
 int net_build(int num_classes, int aux, Net& net);
 
-// A conv(+BN) output in the workspace.
+// the PPM's pooled / branch tensors are bin-major [50][N][C]: bin sizes and first bin per branch
+constexpr int PPM_BINS[4] = {1, 2, 3, 6}, PPM_BASE[4] = {0, 1, 5, 14};
+
+enum { U_CONV0 = 0, U_DW = 1, U_PW = 2 };  // Unit::kind
+
+// A conv+BN output in the workspace, and the layer that produces it.
 struct Unit {
+  int kind = U_PW;          // first conv / depthwise 3x3 / pointwise (GEMM; the aux 3x3 on im2col)
+  const ConvL* conv = nullptr;  // into *Plan::net
+  const BnL* bn = nullptr;
+  int Hi = 0, Wi = 0, Ho = 0, Wo = 0, stride = 0;  // depthwise units: input / output map
   long long M = 0;
   int C = 0, ld = 0;
   size_t z = 0, a = 0;      // raw conv output / activation (same in eval)
@@ -88,6 +97,7 @@ struct Unit {
   // backward wgrads) applies relu(fmaf(z, scale, shift)) to z while staging its operand
   bool lazy = false;
   std::string name;         // reference module path (per-launch profile label)
+  std::string key;          // short name of its debug buffers ("lbe3.z", fscnn_plan_buffer)
   std::string block_name;   // label of a fused whole-block launch (inference bottlenecks)
 };
 
@@ -108,8 +118,8 @@ struct Plan {
   Unit fdw, flow, fhigh;
   Unit c1dw, c1pw, c2dw, c2pw;
   Unit aux0;
-  size_t concat = 0, pooled = 0, feats_a = 0, feats_z = 0, up_low = 0, f = 0, drop = 0,
-         logits = 0, aux_drop = 0, aux_logits = 0, aux_col = 0, pbf = 0, fold_tmp = 0;
+  size_t concat = 0, pooled = 0, feats_a = 0, up_low = 0, f = 0, drop = 0,
+         logits = 0, aux_drop = 0, aux_logits = 0, aux_col = 0, pbf = 0;
   size_t wt = 0;                    // transposed weights (train plans), net.wt_total elements
   size_t lb_we3[9] = {}, lb_wp3[9] = {};  // fp32 inference: split planes of fused bottlenecks
   size_t g_raw = 0, head_part = 0;  // fused loss head (train plans)
@@ -133,8 +143,21 @@ struct Plan {
   std::shared_ptr<SideStream> side;
 };
 
+// Every unit of a plan (Plan& or const Plan&) in forward order; aux0 only for aux nets.  This
+// and plan_build's two allocation sequences are the only places that list the units.  (A
+// function, not a table of Unit* in the plan: plans are copied.)
+template <class P, class F>
+void for_each_unit(P& pl, F&& f) {
+  f(pl.c0); f(pl.l1dw); f(pl.l1pw); f(pl.l2dw); f(pl.l2pw);
+  for (int i = 0; i < 9; ++i) { f(pl.lbe[i]); f(pl.lbd[i]); f(pl.lbp[i]); }
+  for (int i = 0; i < 4; ++i) f(pl.ppk[i]);
+  f(pl.po); f(pl.fdw); f(pl.flow); f(pl.fhigh);
+  f(pl.c1dw); f(pl.c1pw); f(pl.c2dw); f(pl.c2pw);
+  if (pl.net->aux) f(pl.aux0);
+}
+
 int plan_build(const Net& net, int N, int H, int W, int dtype, int train, Plan& pl);
-bool ir_block_shape(const Net& net, const Plan& pl, int i, IrArgs& b);
+bool ir_block_shape(const Plan& pl, int i, IrArgs& b);
 std::shared_ptr<GraphCache> make_graph_cache();
 std::shared_ptr<SideStream> make_side_stream();
 
