@@ -94,6 +94,9 @@ SIGNATURES = {
     "fscnn_backward_loss_dice": (c_int, [c_vp, c_vp, c_vp, c_float, c_float, c_float, c_vp, c_int,
                                          c_vp, c_vp, c_vp, c_vp, c_vp, c_ull, c_float, c_int,
                                          c_int, c_vp]),
+    "fscnn_forward_loss_ohem": (c_int, [c_vp, c_vp, c_int, c_vp, c_ll, c_float, c_ll, c_vp, c_vp,
+                                        c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_ull,
+                                        c_float, c_float, c_vp]),
     "fscnn_backward_dx": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp,
                                   c_vp, c_vp, c_vp, c_ull, c_float, c_int, c_int, c_vp]),
     "fscnn_prof_begin": (c_int, [c_int, c_int]),

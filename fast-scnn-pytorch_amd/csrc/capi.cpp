@@ -831,6 +831,43 @@ int fscnn_backward_loss_dice(const fscnn_plan* plan, const float* grad_loss, con
   GUARD(net_backward(plan->plan, r, stage_from, stage_to));
 }
 
+int fscnn_forward_loss_ohem(const fscnn_plan* plan, const void* x, int x_dtype,
+                            const long long* target, long long ignore_index, float thresh,
+                            long long min_kept, const float* weight, float* loss2, float* prob,
+                            float* thr, unsigned long long* counts, unsigned* work,
+                            const float* params, float* running, long long* nbt, void* ws,
+                            unsigned long long seed, float dropout_p, float momentum,
+                            void* stream) {
+  if (!plan || !x || !target || !loss2 || !prob || !thr || !counts || !work || !params ||
+      !running || !ws) {
+    set_error("fscnn_forward_loss_ohem: null argument");
+    return E_INVALID;
+  }
+  if (min_kept < 0) {
+    set_error("fscnn_forward_loss_ohem: min_kept=%lld", min_kept);
+    return E_INVALID;
+  }
+  // refusals come before anything is launched
+  if (plan->plan.net->aux) {
+    set_error("forward_loss: the fused loss head covers the main output only (aux net)");
+    return E_UNSUPPORTED;
+  }
+  if (!ohem_head_ok(plan->plan.net->num_classes)) {
+    set_error("fscnn_forward_loss_ohem: %d classes (the fused OHEM head takes 1 .. 32)",
+              plan->plan.net->num_classes);
+    return E_UNSUPPORTED;
+  }
+  RunArgs r{};
+  r.x = x; r.x_dtype = x_dtype; r.out = nullptr; r.out_dtype = plan->plan.dtype;
+  r.P = params; r.R = running; r.NBT = nbt; r.ws = ws;
+  r.seed = seed; r.dropout_p = dropout_p; r.momentum = momentum; r.st = S(stream);
+  r.target = target; r.ignore_index = ignore_index; r.loss2 = loss2;
+  r.head = HEAD_OHEM; r.ohem_thresh = thresh; r.ohem_min_kept = min_kept;
+  r.ohem_weight = weight; r.ohem_prob = prob; r.ohem_thr = thr; r.ohem_counts = counts;
+  r.ohem_work = work;
+  GUARD(net_forward(plan->plan, r));
+}
+
 int fscnn_backward_dx(const fscnn_plan* plan, const void* dout, const void* daux,
                       const float* grad_loss, const float* loss2, const void* x, int x_dtype,
                       void* dx, int dx_dtype, const float* params, float* grads, void* ws,

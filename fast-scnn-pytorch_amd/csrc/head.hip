@@ -1163,4 +1163,367 @@ int dice_head_scale(const void* head_ws, void* g, long long M, int C, int ld, co
   return check_launch("dice_head_scale");
 }
 
+// ---- OHEM head (utils/loss.py:127-206, the criterion of train.py:189-191) ----------------------
+// nn.CrossEntropyLoss(weight, ignore_index) over the KEPT pixels of the upsampled logits, a pixel
+// being kept when it is labelled and the softmax probability of its label is <= the threshold of
+// utils/loss.py:159-170.  The same work layout as ce_head_kernel (workgroup = (low-res row,
+// image), thread = low-res column, two logit rows in LDS, every full-resolution pixel once,
+// neighbour shares and the row spill added in a fixed order).  Probabilities are evaluated per
+// pixel (v_exp_f32 / v_rcp_f32) for every plan dtype, so one error bound holds for all of them.
+//   PASS 1: prob[pixel] = p_label (2.0: ignored / out of range) as an fp32 plane, the two integer
+//     counters ohem_threshold_dev reads (#labelled, #(prob <= thresh)), and -- assuming the
+//     threshold will be `thresh`, the common case in training -- the loss partials (sum w nll,
+//     sum w) and g_raw = sum w[t] (softmax - onehot) folded onto the four low-res taps.
+//   ohem_threshold_dev on the plane: *thr = thresh, inf or the k-th smallest probability.
+//   PASS 2: returns at once when *thr is bit-equal to thresh; otherwise recomputes the partials
+//     and g_raw over prob[pixel] <= *thr.  The keep decision is always the comparison of the
+//     STORED fp32 value the select saw, never a re-evaluation, so mask and threshold agree.
+// The gradient has no atomics (the counters are integer adds: exact in any order): two runs give
+// identical bits.
+template <typename T, int CT, bool EXACT, int PASS>
+__global__ __launch_bounds__(HD_T) void ohem_head_kernel(OhemHeadArgs a) {
+  constexpr int SL = (CT % 2 == 0) ? CT + 1 : CT;  // odd LDS stride per column
+  constexpr int CP = (CT + 1) / 2;
+  float thr = a.thresh;
+  if (PASS == 2) {
+    thr = *a.thr;
+    if (__float_as_uint(thr) == __float_as_uint(a.thresh)) return;  // pass 1's result stands
+  }
+  __shared__ float s_L[2 * (HD_T + 1) * SL];
+  __shared__ float s_carry[2 * CT];
+  __shared__ float s_w[CT];
+  __shared__ __attribute__((aligned(8))) signed char s_t[2 * HD_TMAX];
+  __shared__ float s_r1[HD_T], s_r2[HD_T];
+  __shared__ unsigned s_c1[HD_T], s_c2[HD_T];
+  const int tid = threadIdx.x;
+  const int hl = blockIdx.x, n = blockIdx.y;
+  const int Hl = a.Hl, Wl = a.Wl, H = a.H, W = a.W, ldl = a.ldl;
+  const int Cm = EXACT ? CT : a.C;
+  const float sh = ac_scale(Hl, H), sw = ac_scale(Wl, W);
+  const int h_lo = hd_first_ge(hl, Hl, H, sh), h_hi = hd_first_ge(hl + 1, Hl, H, sh);
+  const int hl1 = min(hl + 1, Hl - 1);
+  const T* lg = (const T*)a.logits + (size_t)n * Hl * Wl * ldl;
+  float* g0 = a.g_raw;                              // own-row plane
+  float* g1 = a.g_raw + (size_t)a.N * Hl * Wl * ldl;  // spill plane (row hl+1)
+  const long long* tgt = a.target + (size_t)n * H * W;
+  float* prob = a.prob + (size_t)n * H * W;
+  float loss = 0.f, wsum = 0.f;
+  unsigned nlab = 0u, nle = 0u;
+  if (tid < 2 * CT) s_carry[tid] = 0.f;
+  if (tid < CT) s_w[tid] = (a.weight && tid < Cm) ? a.weight[tid] : 1.f;
+  if (hl == 0) {  // nothing spills into row 0
+    for (int i = tid; i < Wl * ldl; i += HD_T) g1[(size_t)n * Hl * Wl * ldl + i] = 0.f;
+  }
+  // PASS 1 targets: one full-resolution row at a time in LDS as int8 (the next row's loads in
+  // flight during the current row), from the plan's packed int8 copy (8 per thread) or the int64
+  // rows; rows wider than HD_TMAX are read per pixel.  PASS 2 reads the targets of kept pixels only.
+  const bool lds_t = PASS == 1 && W <= HD_TMAX;
+  const bool t8 = a.tgt8 != nullptr && W <= HD_TMAX && W % 8 == 0;
+  const bool t8own = tid * 8 < W;
+  const signed char* tgt8 = a.tgt8 + (size_t)n * H * W;
+  constexpr int TPT = HD_TMAX / HD_T;
+  for (int cb = 0; cb < Wl; cb += HD_T) {
+    __syncthreads();
+    for (int i = tid; i < 2 * (HD_T + 1) * CT; i += HD_T) {
+      const int c = i % CT, jr = i / CT;
+      const int j = jr % (HD_T + 1), r = jr / (HD_T + 1);
+      const int col = min(cb + j, Wl - 1);
+      const int row = r ? hl1 : hl;
+      // staged in log2 units: the softmax runs on v_exp_f32 (2^x)
+      s_L[(r * (HD_T + 1) + j) * SL + c] =
+          c < Cm ? ld1(lg + ((size_t)row * Wl + col) * ldl + c) * HD_LOG2E : 0.f;
+    }
+    __syncthreads();
+    const int t = cb + tid;
+    const bool active = t < Wl;
+    f32x2 a0[CT], a1[CT];  // (acc00, acc01) own row, columns t / t+1; (acc10, acc11) row hl+1
+#pragma unroll
+    for (int c = 0; c < CT; ++c) a0[c] = a1[c] = f32x2{0.f, 0.f};
+    const int w_lo = active ? hd_first_ge(t, Wl, W, sw) : 0;
+    const int w_hi = active ? hd_first_ge(t + 1, Wl, W, sw) : 0;
+    int tnext[TPT];
+    uint2 tq = make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
+    auto load_trow = [&](int h) {
+      if (t8) {
+        if (t8own) tq = *reinterpret_cast<const uint2*>(tgt8 + (size_t)h * W + tid * 8);
+        return;
+      }
+      const long long* tr = tgt + (size_t)h * W;
+#pragma unroll
+      for (int k = 0; k < TPT; ++k) {
+        const int w = tid + HD_T * k;
+        const long long tg = tr[w < W ? w : 0];
+        tnext[k] = (w < W && tg != a.ignore_index && tg >= 0 && tg < Cm) ? (int)tg : -1;
+      }
+    };
+    if (lds_t && h_lo < h_hi) load_trow(h_lo);
+    const float* L0 = &s_L[tid * SL];
+    const float* L1 = &s_L[((HD_T + 1) + tid) * SL];
+    for (int h = h_lo; h < h_hi; ++h) {
+      signed char* trow_s = s_t + (h & 1) * HD_TMAX;
+      if (lds_t) {  // (uniform: every thread of the workgroup takes the barrier)
+        if (t8) {
+          if (t8own) *reinterpret_cast<uint2*>(trow_s + tid * 8) = tq;
+        } else {
+#pragma unroll
+          for (int k = 0; k < TPT; ++k)
+            if (tid + HD_T * k < W) trow_s[tid + HD_T * k] = (signed char)tnext[k];
+        }
+        __syncthreads();
+        if (h + 1 < h_hi) load_trow(h + 1);
+      }
+      if (active) {
+        const Lerp lh = ac_lerp(h, Hl, H, sh);
+        // class pairs: v0 = the row-interpolated logits of column t, dv = (column t+1) - v0
+        f32x2 v0[CP], dv[CP];
+        const f32x2 h0 = {lh.l0, lh.l0}, h1 = {lh.l1, lh.l1};
+#pragma unroll
+        for (int p = 0; p < CP; ++p) {
+          const int c = 2 * p, c1 = c + 1 < CT ? c + 1 : c;
+          const f32x2 l00 = {L0[c], c + 1 < CT ? L0[c1] : 0.f};
+          const f32x2 l10 = {L1[c], c + 1 < CT ? L1[c1] : 0.f};
+          const f32x2 l01 = {L0[SL + c], c + 1 < CT ? L0[SL + c1] : 0.f};
+          const f32x2 l11 = {L1[SL + c], c + 1 < CT ? L1[SL + c1] : 0.f};
+          v0[p] = __builtin_elementwise_fma(h1, l10, h0 * l00);
+          dv[p] = __builtin_elementwise_fma(h1, l11, h0 * l01) - v0[p];
+        }
+        const long long* trow = tgt + (size_t)h * W;
+        float* prow = prob + (size_t)h * W;
+        for (int w = w_lo; w < w_hi; ++w) {
+          int ti;
+          float pv = 2.f;
+          if (PASS == 1) {
+            if (lds_t) {
+              ti = trow_s[w];
+            } else {
+              const long long tg = trow[w];
+              ti = (tg != a.ignore_index && tg >= 0 && tg < Cm) ? (int)tg : -1;
+            }
+            if (ti < 0) {  // ignored: sorts after every probability, never kept
+              prow[w] = 2.f;
+              continue;
+            }
+          } else {
+            pv = prow[w];
+            if (!(pv <= thr && pv < 1.5f)) continue;  // not kept (2.0: ignored, also under inf)
+            ti = t8 ? (int)tgt8[(size_t)h * W + w] : (int)trow[w];
+            ti = min(max(ti, 0), Cm - 1);  // (a kept pixel is a labelled one: already in range)
+          }
+          const Lerp lw = ac_lerp(w, Wl, W, sw);
+          const f32x2 w1 = {lw.l1, lw.l1};
+          f32x2 e[CP];
+#pragma unroll
+          for (int p = 0; p < CP; ++p) e[p] = __builtin_elementwise_fma(w1, dv[p], v0[p]);
+          float mx = -INFINITY;
+#pragma unroll
+          for (int p = 0; p < CP; ++p) {
+            if (2 * p < Cm) mx = fmaxf(mx, e[p].x);
+            if (2 * p + 1 < Cm) mx = fmaxf(mx, e[p].y);
+          }
+          // the target's logit, re-interpolated from the staged rows with the same operations
+          float lt;
+          {
+            const float v0t = fmaf(lh.l1, L1[ti], lh.l0 * L0[ti]);
+            const float v1t = fmaf(lh.l1, L1[SL + ti], lh.l0 * L0[SL + ti]);
+            lt = fmaf(lw.l1, v1t - v0t, v0t);
+          }
+          float se = 0.f;
+#pragma unroll
+          for (int p = 0; p < CP; ++p) {
+            e[p].x = 2 * p < Cm ? __builtin_amdgcn_exp2f(e[p].x - mx) : 0.f;
+            e[p].y = 2 * p + 1 < Cm ? __builtin_amdgcn_exp2f(e[p].y - mx) : 0.f;
+            se += e[p].x + e[p].y;
+          }
+          const float inv = __builtin_amdgcn_rcpf(se);  // v_rcp_f32 (1 ulp)
+          if (PASS == 1) {
+            pv = __builtin_amdgcn_exp2f(lt - mx) * inv;
+            prow[w] = pv;
+            nlab += 1u;
+            if (!(pv <= thr)) continue;  // the comparison of the value just stored
+            nle += 1u;
+          }
+          const float wt = s_w[ti];
+          loss = fmaf(wt, (mx - lt + __builtin_amdgcn_logf(se)) * HD_LN2, loss);
+          wsum += wt;
+          const f32x2 k0 = {lh.l0 * lw.l0, lh.l0 * lw.l1};
+          const f32x2 k1 = {lh.l1 * lw.l0, lh.l1 * lw.l1};
+          const f32x2 iv = {inv * wt, inv * wt};
+#pragma unroll
+          for (int p = 0; p < CP; ++p) {
+            const f32x2 oh = {2 * p == ti ? wt : 0.f, 2 * p + 1 == ti ? wt : 0.f};
+            const f32x2 g = e[p] * iv - oh;
+            const f32x2 gx = {g.x, g.x}, gy = {g.y, g.y};
+            a0[2 * p] = __builtin_elementwise_fma(k0, gx, a0[2 * p]);
+            a1[2 * p] = __builtin_elementwise_fma(k1, gx, a1[2 * p]);
+            if (2 * p + 1 < CT) {
+              a0[2 * p + 1] = __builtin_elementwise_fma(k0, gy, a0[2 * p + 1]);
+              a1[2 * p + 1] = __builtin_elementwise_fma(k1, gy, a1[2 * p + 1]);
+            }
+          }
+        }
+      }
+    }
+    float acc00[CT], acc01[CT], acc10[CT], acc11[CT];
+#pragma unroll
+    for (int c = 0; c < CT; ++c) {
+      acc00[c] = a0[c].x;
+      acc01[c] = a0[c].y;
+      acc10[c] = a1[c].x;
+      acc11[c] = a1[c].y;
+    }
+    if (active) {
+      if (t == Wl - 1) {  // i1(w) == i0(w) on the last column: both taps are column t
+#pragma unroll
+        for (int c = 0; c < CT; ++c) {
+          acc00[c] += acc01[c];
+          acc10[c] += acc11[c];
+          acc01[c] = acc11[c] = 0.f;
+        }
+      }
+      if (hl1 == hl) {  // last row: both row taps are row hl
+#pragma unroll
+        for (int c = 0; c < CT; ++c) {
+          acc00[c] += acc10[c];
+          acc01[c] += acc11[c];
+          acc10[c] = acc11[c] = 0.f;
+        }
+      }
+    }
+    // ---- hand the (*, t+1) shares to thread t+1 through LDS -------------------------------
+    __syncthreads();
+#pragma unroll
+    for (int c = 0; c < CT; ++c) {
+      s_L[tid * SL + c] = acc01[c];
+      s_L[((HD_T + 1) + tid) * SL + c] = acc11[c];
+    }
+    __syncthreads();
+    if (active) {
+      float* o0 = g0 + (((size_t)n * Hl + hl) * Wl + t) * ldl;
+      float* o1 = g1 + (((size_t)n * Hl + hl + 1) * Wl + t) * ldl;
+#pragma unroll
+      for (int c = 0; c < CT; ++c) {
+        if (c < Cm) {
+          const float left0 = tid > 0 ? s_L[(tid - 1) * SL + c] : s_carry[c];
+          const float left1 = tid > 0 ? s_L[((HD_T + 1) + tid - 1) * SL + c] : s_carry[CT + c];
+          o0[c] = acc00[c] + left0;
+          if (hl1 != hl) o1[c] = acc10[c] + left1;
+        }
+      }
+    }
+    __syncthreads();
+    if (tid == HD_T - 1) {  // column cb + HD_T starts the next chunk
+#pragma unroll
+      for (int c = 0; c < CT; ++c) {
+        s_carry[c] = acc01[c];
+        s_carry[CT + c] = acc11[c];
+      }
+    }
+  }
+  s_r1[tid] = loss;
+  s_r2[tid] = wsum;
+  s_c1[tid] = nlab;
+  s_c2[tid] = nle;
+  __syncthreads();
+  for (int off = HD_T / 2; off > 0; off >>= 1) {
+    if (tid < off) {
+      s_r1[tid] += s_r1[tid + off];
+      s_r2[tid] += s_r2[tid + off];
+      s_c1[tid] += s_c1[tid + off];
+      s_c2[tid] += s_c2[tid + off];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const size_t pi = (size_t)n * Hl + hl;
+    a.part[2 * pi] = s_r1[0];
+    a.part[2 * pi + 1] = s_r2[0];
+    if (PASS == 1) {
+      if (s_c1[0]) atomicAdd(&a.counts[0], (unsigned long long)s_c1[0]);
+      if (s_c2[0]) atomicAdd(&a.counts[1], (unsigned long long)s_c2[0]);
+    }
+  }
+}
+
+// the counters are zeroed inside the run (the library replays its runs as captured graphs)
+__global__ void ohem_head_zero_kernel(unsigned long long* counts) {
+  if (threadIdx.x < 2) counts[threadIdx.x] = 0ull;
+}
+
+// out2 = (weighted mean loss, sum of kept weights) as ce_head_finalize_kernel; with thr given
+// (pass 2) nothing is written when *thr is bit-equal to thresh
+__global__ __launch_bounds__(256) void ohem_head_finalize_kernel(const float* part, int P,
+                                                                 const float* thr, float thresh,
+                                                                 float* out) {
+  if (thr && __float_as_uint(*thr) == __float_as_uint(thresh)) return;
+  __shared__ double r1[256], r2[256];
+  double s1 = 0.0, s2 = 0.0;
+  for (int p = threadIdx.x; p < P; p += 256) {
+    s1 += part[2 * p];
+    s2 += part[2 * p + 1];
+  }
+  r1[threadIdx.x] = s1;
+  r2[threadIdx.x] = s2;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (threadIdx.x < off) {
+      r1[threadIdx.x] += r1[threadIdx.x + off];
+      r2[threadIdx.x] += r2[threadIdx.x + off];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    out[0] = r2[0] > 0 ? (float)(r1[0] / r2[0]) : NAN;
+    out[1] = (float)r2[0];
+  }
+}
+
+template <int CT, bool EXACT, int PASS>
+static void ohem_head_launch_dt(const OhemHeadArgs& a, int dtype, dim3 grid, hipStream_t st) {
+  if (dtype == DT_F32) prof_launch((ohem_head_kernel<float, CT, EXACT, PASS>), grid, HD_T, 0, st, a);
+  else if (dtype == DT_F16) prof_launch((ohem_head_kernel<f16, CT, EXACT, PASS>), grid, HD_T, 0, st, a);
+  else prof_launch((ohem_head_kernel<bf16, CT, EXACT, PASS>), grid, HD_T, 0, st, a);
+}
+template <int PASS>
+static void ohem_head_launch_c(const OhemHeadArgs& a, int dtype, dim3 grid, hipStream_t st) {
+  if (a.C == 19) ohem_head_launch_dt<19, true, PASS>(a, dtype, grid, st);
+  else if (a.C == 2) ohem_head_launch_dt<2, true, PASS>(a, dtype, grid, st);
+  else if (a.C <= 8) ohem_head_launch_dt<8, false, PASS>(a, dtype, grid, st);
+  else ohem_head_launch_dt<HD_CMAX, false, PASS>(a, dtype, grid, st);
+}
+
+bool ohem_head_ok(int C) { return C >= 1 && C <= HD_CMAX; }
+
+int ohem_head(const OhemHeadArgs& a, long long min_kept, unsigned* work, float* out2, int dtype,
+              hipStream_t st) {
+  if (!ohem_head_ok(a.C)) {
+    set_error("ohem_head: %d classes (max %d)", a.C, HD_CMAX);
+    return E_UNSUPPORTED;
+  }
+  if (min_kept < 0 || !a.prob || !a.thr || !a.counts || !work) {
+    set_error("ohem_head: min_kept=%lld / null buffer", min_kept);
+    return E_INVALID;
+  }
+  const dim3 grid(a.Hl, a.N);
+  const int P = ce_head_parts(a.N, a.Hl, a.Wl);
+  const double npix = (double)a.N * a.H * a.W, M = (double)a.N * a.Hl * a.Wl;
+  {
+    ProfScope ps(PK_CE, st, (dtype == DT_F32 ? 4.0 : 2.0) * M * a.C + (a.tgt8 ? 1.0 : 8.0) * npix +
+                                4.0 * npix + 2.0 * 4.0 * M * a.C, 0.0);
+    prof_launch(ohem_head_zero_kernel, 1, 64, 0, st, a.counts);
+    ohem_head_launch_c<1>(a, dtype, grid, st);
+    if (int rc = check_launch("ohem_head (pass 1)")) return rc;
+    prof_launch(ohem_head_finalize_kernel, 1, 256, 0, st, a.part, P, (const float*)nullptr,
+                a.thresh, out2);
+    if (int rc = check_launch("ohem_head_finalize")) return rc;
+  }
+  if (int rc = ohem_threshold_dev(a.prob, (long long)npix, a.counts, min_kept, a.thresh, work,
+                                  const_cast<float*>(a.thr), st))
+    return rc;
+  ProfScope ps(PK_CE, st, 4.0 * npix, 0.0);
+  ohem_head_launch_c<2>(a, dtype, grid, st);
+  if (int rc = check_launch("ohem_head (pass 2)")) return rc;
+  prof_launch(ohem_head_finalize_kernel, 1, 256, 0, st, a.part, P, a.thr, a.thresh, out2);
+  return check_launch("ohem_head_finalize (pass 2)");
+}
+
 }  // namespace fscnn

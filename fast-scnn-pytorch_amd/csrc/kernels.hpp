@@ -369,6 +369,25 @@ struct DiceHeadArgs {
   const double* stats = nullptr;  // (I, S, T, F), written by the finalize
 };
 
+// Fused OHEM training head (head.hip): CeHeadArgs' upsample + loss + low-res gradient for
+// SoftmaxCrossEntropyOHEMLoss (utils/loss.py:127-176): weighted CE over the labelled pixels whose
+// label probability is <= the device threshold *thr (ohem_threshold_dev on the prob plane).
+struct OhemHeadArgs {
+  int N, C, Hl, Wl, H, W;
+  const void* logits;        // NHWC [N][Hl][Wl][ldl]
+  int ldl;
+  const long long* target;   // [N][H][W]
+  long long ignore_index;
+  const signed char* tgt8 = nullptr;  // optional packed targets (ce_pack_targets, ignore = -1)
+  const float* weight = nullptr;      // device [C] class weights or null
+  float thresh = 0.7f;
+  float* prob = nullptr;     // [N][H][W] fp32: label probability, 2.0 = ignored
+  const float* thr = nullptr;           // device scalar, written between the passes
+  unsigned long long* counts = nullptr;  // [2]: #labelled, #(prob <= thresh)
+  float* g_raw = nullptr;    // 2 planes NHWC [N][Hl][Wl][ldl] fp32: own row, spill from row above
+  float* part = nullptr;     // [N * Hl][2]: sum w nll, sum w over the kept pixels
+};
+
 // Fused validation head (evalhead.hip): upsample + criterion loss + SegmentationMetric counters
 // from the low-res logits of an inference plan; no full-resolution tensor is written.
 struct EvalHeadArgs {
@@ -700,6 +719,12 @@ int dice_head(const DiceHeadArgs& a, void* head_ws, float* loss, double* stats, 
 int dice_head_scale(const void* head_ws, void* g, long long M, int C, int ld, const float* gout,
                     const double* stats, float smooth, float wd, float wf, double npix, int dtype,
                     hipStream_t st);
+// OHEM head: loss2 = (weighted mean loss over the kept pixels, sum of kept weights) and g_raw in
+// the CE head's format (ce_head_scale finishes it); prob / thr / counts / work as for ohem_prob /
+// ohem_threshold_dev, the counters zeroed by the call.  ohem_head_ok: 1 .. 32 classes.
+bool ohem_head_ok(int C);
+int ohem_head(const OhemHeadArgs& a, long long min_kept, unsigned* work, float* out2, int dtype,
+              hipStream_t st);
 // Validation head: eval_head_ok tells whether the kernel takes the geometry (staged rows in LDS,
 // 1 .. 32 classes, Dice from 2); eval_head returns E_UNSUPPORTED otherwise
 int eval_head_parts(int N, int H, int W);

@@ -1284,6 +1284,17 @@ struct Exec {
         h.smooth = r.smooth; h.wd = r.dice_weight; h.wf = r.focal_weight;
         return dice_head(h, r.head_ws, r.loss2, r.dice_stats, dt, r.st);
       }
+      if (r.head == HEAD_OHEM) {
+        g_prof_tag = "head (upsample + OHEM cross entropy)";
+        OhemHeadArgs h{};
+        h.N = N; h.C = net.num_classes; h.Hl = pl.H3; h.Wl = pl.W3; h.H = pl.H; h.W = pl.W;
+        h.logits = W(pl.logits); h.ldl = pl.Cp; h.target = r.target; h.ignore_index = r.ignore_index;
+        if (pack) h.tgt8 = (const signed char*)W(pl.tgt8);
+        h.weight = r.ohem_weight; h.thresh = r.ohem_thresh; h.prob = r.ohem_prob;
+        h.thr = r.ohem_thr; h.counts = r.ohem_counts;
+        h.g_raw = Wf(pl.g_raw); h.part = Wf(pl.head_part);
+        return ohem_head(h, r.ohem_min_kept, r.ohem_work, r.loss2, dt, r.st);
+      }
       g_prof_tag = "head (upsample + cross entropy)";
       CeHeadArgs h{};
       h.N = N; h.C = net.num_classes; h.Hl = pl.H3; h.Wl = pl.W3; h.H = pl.H; h.W = pl.W;
@@ -1952,7 +1963,9 @@ std::vector<uint64_t> run_key(int kind, int s0, int s1, const RunArgs& r) {
           P(r.bws), P(r.dout), P(r.daux), fbits(r.dropout_p), fbits(r.momentum), P(r.target),
           (uint64_t)r.ignore_index, P(r.loss2), P(r.gloss), P(r.dx), (uint64_t)r.dx_dtype,
           (uint64_t)r.head, fbits(r.smooth), fbits(r.dice_weight), fbits(r.focal_weight),
-          fbits(r.alpha), fbits(r.gamma), P(r.head_ws), P(r.dice_stats), (uint64_t)r.validate,
+          fbits(r.alpha), fbits(r.gamma), P(r.head_ws), P(r.dice_stats), fbits(r.ohem_thresh),
+          (uint64_t)r.ohem_min_kept, P(r.ohem_weight), P(r.ohem_prob), P(r.ohem_thr),
+          P(r.ohem_counts), P(r.ohem_work), (uint64_t)r.validate,
           fbits(r.aux_weight), P(r.counts), (uint64_t)r.e2e_ho, (uint64_t)r.e2e_wo,
           (uint64_t)r.e2e_softmax, (uint64_t)r.e2e_pdtype, (uint64_t)r.e2e_scale, P(r.e2e_probs),
           P(r.e2e_labels), (uint64_t)r.bev_hb, (uint64_t)r.bev_wb, (uint64_t)r.bev_min_width,

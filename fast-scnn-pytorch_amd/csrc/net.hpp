@@ -161,7 +161,7 @@ bool ir_block_shape(const Plan& pl, int i, IrArgs& b);
 std::shared_ptr<GraphCache> make_graph_cache();
 std::shared_ptr<SideStream> make_side_stream();
 
-enum { HEAD_CE = 0, HEAD_DICE = 1 };
+enum { HEAD_CE = 0, HEAD_DICE = 1, HEAD_OHEM = 2 };
 
 struct RunArgs {
   const void* x; int x_dtype;     // NCHW input image
@@ -194,6 +194,17 @@ struct RunArgs {
   float smooth = 1e-6f, dice_weight = 1.f, focal_weight = 0.f, alpha = 0.5f, gamma = 2.f;
   void* head_ws = nullptr;
   double* dice_stats = nullptr;
+  // HEAD_OHEM (utils/loss.py:127-206): weighted CE over the labelled pixels whose label
+  // probability is <= the OHEM threshold; loss2 = (weighted mean, sum of kept weights), so the
+  // backward is the CE head's.  Caller-owned device buffers: the probability plane [N H W], the
+  // threshold scalar, the two counters (zeroed inside the run) and the select's 2056-word scratch.
+  float ohem_thresh = 0.7f;
+  long long ohem_min_kept = 0;
+  const float* ohem_weight = nullptr;
+  float* ohem_prob = nullptr;
+  float* ohem_thr = nullptr;
+  unsigned long long* ohem_counts = nullptr;
+  unsigned* ohem_work = nullptr;
   // eval prediction: forward with labels != null writes argmax(upsampled logits) instead of out
   void* labels = nullptr;
   int label_u8 = 0;

@@ -154,3 +154,10 @@ class DistributedFastSCNN(torch.nn.Module):
         under the reference's DistributedDataParallel: the averaged gradient is the mean of the
         per-rank Dice gradients, not the gradient of one Dice over the global batch."""
         return self.module.forward_loss(x, target, ignore_index=ignore_index, criterion=criterion)
+
+    def forward_loss_ohem(self, x, target, criterion):
+        """Fused forward + OHEM loss of the local shard (``FastSCNN.forward_loss_ohem``); backward
+        all-reduces gradients per stage.  The threshold rule (``min_kept``, the k-th smallest
+        label probability) runs over this rank's shard, as it does per replica under the
+        reference's DistributedDataParallel."""
+        return self.module.forward_loss_ohem(x, target, criterion)

@@ -298,8 +298,9 @@ def _head_spec(criterion, ignore_index=-1):
         return ("ce", int(ignore_index))
     names = [c.__name__ for c in type(criterion).__mro__]
     if "SoftmaxCrossEntropyOHEMLoss" in names or "MixSoftmaxCrossEntropyOHEMLoss" in names:
-        raise RuntimeError("forward_loss: the OHEM criterion has no fused loss head; use the "
-                           "unfused path, criterion(model(x), target)")
+        raise RuntimeError("forward_loss: the OHEM criterion has no fused loss head here; use "
+                           "forward_loss_ohem(x, target, criterion), or the unfused path, "
+                           "criterion(model(x), target)")
     if "FocalDiceLoss" in names:
         inner = getattr(criterion, "dice_loss", None)  # the reference keeps smooth there
         smooth = inner.smooth if inner is not None else criterion.smooth
@@ -316,16 +317,44 @@ def _head_spec(criterion, ignore_index=-1):
                        "criterion(model(x), target)" % type(criterion).__name__)
 
 
+def _ohem_spec(criterion):
+    """The fused OHEM head's arguments of a criterion object, as the tuple
+    ``("ohem", ignore_label, thresh, min_kept, weight_or_None)``.
+
+    Duck-typed like ``_head_spec``: ``SoftmaxCrossEntropyOHEMLoss`` /
+    ``MixSoftmaxCrossEntropyOHEMLoss`` of this package (class weights in ``.weight``) or of
+    utils/loss.py:127-206 (class weights in ``.criterion.weight``, the inner
+    ``nn.CrossEntropyLoss``).  Anything else raises ``RuntimeError``."""
+    names = [c.__name__ for c in type(criterion).__mro__]
+    if "SoftmaxCrossEntropyOHEMLoss" not in names and "MixSoftmaxCrossEntropyOHEMLoss" not in names:
+        raise RuntimeError("forward_loss_ohem: %s is not the OHEM criterion "
+                           "(SoftmaxCrossEntropyOHEMLoss / MixSoftmaxCrossEntropyOHEMLoss); use "
+                           "forward_loss, or the unfused path, criterion(model(x), target)"
+                           % type(criterion).__name__)
+    try:
+        inner = getattr(criterion, "criterion", None)  # the reference keeps the weights there
+        weight = inner.weight if inner is not None else criterion.weight
+        return ("ohem", int(criterion.ignore_label), float(criterion.thresh),
+                int(criterion.min_kept), weight)
+    except AttributeError as e:
+        raise RuntimeError("forward_loss_ohem: %s lacks the OHEM criterion's attributes (%s); "
+                           "use the unfused path, criterion(model(x), target)"
+                           % (type(criterion).__name__, e))
+
+
 class _FastSCNNLossFunction(torch.autograd.Function):
     """Fused train step head: loss = criterion(upsample(logits_lowres), target) at low
-    resolution.  ``head`` is the CE head's ignore_index (an int) or a Dice ``_head_spec`` tuple;
-    the Dice head's coefficient planes (``head_ws``) and sums (``stats``) travel to the backward
-    in ``ctx.dice``."""
+    resolution.  ``head`` is the CE head's ignore_index (an int), a Dice ``_head_spec`` tuple or
+    an ``_ohem_spec`` tuple (its weights on the device); the Dice head's coefficient planes
+    (``head_ws``) and sums (``stats``) travel to the backward in ``ctx.dice``.  The OHEM head
+    leaves ``loss2`` and the low-res gradient planes in the CE head's format: same backward."""
 
     @staticmethod
     def forward(ctx, x, target, head, model, ar, *params):
         ctx.dice = None
-        if isinstance(head, tuple):
+        if isinstance(head, tuple) and head[0] == "ohem":
+            loss2, ws, seed, dt, xc = model._run_forward_loss_ohem(x, target, head, ar)
+        elif isinstance(head, tuple):
             if ctx.needs_input_grad[0]:
                 raise RuntimeError("forward_loss: the fused Dice head does not form the input "
                                    "image's gradient; use criterion(model(x), target)")
@@ -865,8 +894,9 @@ class FastSCNN(nn.Module):
         Otherwise the criterion object the training script built, this package's or the
         reference's own (``_head_spec``): ``DiceLoss``, ``MixDiceLoss`` and ``FocalDiceLoss``
         (utils/loss.py:12-100) take the fused Dice head, ``MixSoftmaxCrossEntropyLoss`` the CE
-        head with the criterion's ``ignore_index``; the OHEM criterion and anything else raise
-        ``RuntimeError`` (use ``criterion(model(x), target)``).
+        head with the criterion's ``ignore_index``; the OHEM criterion (its fused head is
+        ``forward_loss_ohem``) and anything else raise ``RuntimeError`` (use
+        ``criterion(model(x), target)``).
 
         Dice targets outside ``[0, num_classes)`` are a caller error, as in the reference (its
         focal term raises): with ``loss.CHECK_TARGETS`` they raise ``IndexError``, otherwise they
@@ -879,6 +909,110 @@ class FastSCNN(nn.Module):
         if criterion is not None:
             spec = _head_spec(criterion, ignore_index)
             head = spec[1] if spec[0] == "ce" else spec
+        ar = self._exec_arena(x.device)
+        return _FastSCNNLossFunction.apply(x, target, head, self, ar, *ar["params"])
+
+    def _ohem_weight(self, weight, device):
+        """The criterion's class weights as a device fp32 vector, moved once per (tensor,
+        version, device) and kept on the model: later steps do no H2D copy."""
+        if weight is None:
+            return None
+        if weight.numel() != self.num_classes:
+            raise RuntimeError("weight tensor should be defined either for all %d classes or no "
+                               "classes but got weight tensor of shape: [%d]"
+                               % (self.num_classes, weight.numel()))
+        if weight.device == device and weight.dtype == torch.float32 and weight.is_contiguous():
+            return weight.detach()
+        cache = self.__dict__.setdefault("_ohem_wcache", {})
+        key = (id(weight), weight._version, str(device))
+        hit = cache.get(key)
+        if hit is None or hit[0] is not weight:
+            cache.clear()
+            hit = cache[key] = (weight, weight.detach().to(device=device, dtype=torch.float32)
+                                .contiguous())
+        return hit[1]
+
+    def _run_forward_loss_ohem(self, x, target, spec, ar):
+        """The forward of the fused OHEM head (``spec``: an ``_ohem_spec`` tuple whose weights
+        are on the device)."""
+        if self.aux:
+            raise RuntimeError("forward_loss_ohem: the fused loss head covers the main output "
+                               "only; with aux=True use MixSoftmaxCrossEntropyOHEMLoss(aux=True)"
+                               "(model(x), target)")
+        if not x.is_cuda or not target.is_cuda:
+            raise RuntimeError("FastSCNN.forward_loss_ohem: the HIP path needs ROCm device tensors")
+        nat = self.native()
+        N, _, H, W = x.shape
+        if tuple(target.shape) != (N, H, W):
+            raise RuntimeError("forward_loss_ohem: target %s does not match input %s"
+                               % (tuple(target.shape), tuple(x.shape)))
+        if N < 2:
+            raise ValueError("Expected more than 1 value per channel when training, got input "
+                             "size torch.Size([1, 32, 1, 1])")
+        _, ignore_index, thresh, min_kept, weight = spec
+        dt = self._compute_dtype(x, True)
+        x = self._input(x)
+        target = target.to(torch.int64).contiguous()
+        from . import loss as _loss
+        if _loss.CHECK_TARGETS:
+            _loss.check_targets(target, self.num_classes, ignore_index)
+        plan, fw, _ = nat.plan(N, H, W, _lib.dtype_code(dt), True, x.device)
+        dev = x.device
+        ws = torch.empty(max(fw, 1), dtype=torch.uint8, device=dev)
+        loss2 = torch.empty(2, dtype=torch.float32, device=dev)
+        prob = torch.empty(N * H * W, dtype=torch.float32, device=dev)
+        thr = torch.empty(1, dtype=torch.float32, device=dev)
+        counts = torch.empty(2, dtype=torch.int64, device=dev)  # zeroed inside the native run
+        work = torch.empty(2056, dtype=torch.int32, device=dev)
+        p = self._dropout_p()
+        seed = 0
+        if p > 0:
+            fixed = getattr(self, "_dropout_seed", None)
+            seed = int(fixed) if fixed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
+        with torch.cuda.device(dev):
+            rc = _lib.load().fscnn_forward_loss_ohem(
+                plan, _lib.ptr(x), _lib.dtype_code(x.dtype), _lib.ptr(target), int(ignore_index),
+                _lib.c_float(thresh), int(min_kept),
+                _lib.ptr(weight) if weight is not None else None, _lib.ptr(loss2),
+                _lib.ptr(prob), _lib.ptr(thr), _lib.ptr(counts), _lib.ptr(work),
+                _lib.ptr(ar["P"]), _lib.ptr(ar["R"]), _lib.ptr(ar["NBT"]), _lib.ptr(ws),
+                _lib.c_ull(seed), _lib.c_float(p), _lib.c_float(self._momentum()),
+                _lib.stream_ptr(dev))
+        if rc == -2:  # E_UNSUPPORTED: nothing was launched
+            raise RuntimeError("forward_loss_ohem: no fused OHEM head for this model (%s); use "
+                               "the unfused path, criterion(model(x), target)"
+                               % _lib.load().fscnn_last_error().decode(errors="replace"))
+        _lib.check(rc, "fscnn_forward_loss_ohem")
+        self._writeback(ar)
+        torch.autograd.graph.increment_version(ar["R"])
+        if getattr(self, "_keep_ws", False):
+            self._debug = {"plan": plan, "ws": ws, "dt": dt,
+                           "ohem": {"prob": prob.view(N, H, W), "thr": thr, "counts": counts}}
+        return loss2, ws, seed, dt, x
+
+    def forward_loss_ohem(self, x, target, criterion):
+        """Fused train-step head for the OHEM criterion: ``criterion(self(x), target)`` of
+        train.py:189-191 / 270-271 with ``SoftmaxCrossEntropyOHEMLoss`` /
+        ``MixSoftmaxCrossEntropyOHEMLoss`` (this package's or the reference's own object,
+        ``_ohem_spec``), computed from the low-res logits without materialising full-resolution
+        logits or their gradient.  Returns the scalar loss; requires train mode.
+
+        The label probabilities, the threshold rule (``thresh``, ``min_kept``) and the class
+        weights all stay on the device: no host synchronisation in forward or backward.  The
+        loss covers the main output only (``aux=True`` models raise); targets outside
+        ``[0, num_classes)`` count as ignored (``loss.CHECK_TARGETS`` raises instead).
+        ``forward_loss(criterion=<OHEM>)`` and ``validate`` keep refusing the criterion: this
+        method is the head's one entry."""
+        spec = _ohem_spec(criterion)
+        if not self.training:
+            raise RuntimeError("forward_loss_ohem is the training step; call model.train() first")
+        if not x.is_cuda:
+            raise RuntimeError("FastSCNN.forward_loss_ohem: the HIP path needs ROCm device tensors")
+        if self.aux:
+            raise RuntimeError("forward_loss_ohem: the fused loss head covers the main output "
+                               "only; with aux=True use MixSoftmaxCrossEntropyOHEMLoss(aux=True)"
+                               "(model(x), target)")
+        head = spec[:4] + (self._ohem_weight(spec[4], x.device),)
         ar = self._exec_arena(x.device)
         return _FastSCNNLossFunction.apply(x, target, head, self, ar, *ar["params"])
 

@@ -369,6 +369,30 @@ int fscnn_backward_loss_dice(const fscnn_plan* plan, const float* grad_loss, con
                              void* head_ws, unsigned long long dropout_seed, float dropout_p,
                              int stage_from, int stage_to, void* stream);
 
+/* The same fused step head for the OHEM criterion (SoftmaxCrossEntropyOHEMLoss /
+ * MixSoftmaxCrossEntropyOHEMLoss, utils/loss.py:127-206, what train.py:189-191 builds):
+ * nn.CrossEntropyLoss(weight, ignore_index) over the kept pixels of the upsampled logits, a pixel
+ * being kept when it is labelled and the softmax probability of its label is <= the threshold
+ * of fscnn_ohem_threshold (inf, thresh, or the min_kept-th smallest label probability).  One
+ * pass over the low-resolution logits writes prob[N*H*W] (fp32; 2.0 for ignored or out-of-range
+ * targets, as fscnn_ohem_prob) and the two counters, and forms loss and gradient for the
+ * threshold `thresh`; the threshold rule runs on the plane; a second pass, which returns at once
+ * when *thr is bit-equal to thresh, redoes loss and gradient over prob[i] <= *thr.
+ * loss2[0] = weighted mean loss over the kept pixels (NaN when none), loss2[1] = the sum of their
+ * class weights (their count when weight is null): the CE head's format, so the backward is
+ * fscnn_backward_loss / fscnn_backward_dx with this loss2.  weight: device float[num_classes] or
+ * null.  prob, thr (float[1]), counts (uint64[2], zeroed by the call) and work (2056 uint32) are
+ * caller-owned device buffers with the sizes of fscnn_ohem_prob / fscnn_ohem_threshold; nothing
+ * is read back by the host.  num_classes 1 .. 32; more classes or an aux net return -2 before
+ * anything is launched. */
+int fscnn_forward_loss_ohem(const fscnn_plan* plan, const void* x, int x_dtype,
+                            const long long* target, long long ignore_index, float thresh,
+                            long long min_kept, const float* weight, float* loss2, float* prob,
+                            float* thr, unsigned long long* counts, unsigned* work,
+                            const float* params, float* running, long long* nbt, void* ws,
+                            unsigned long long dropout_seed, float dropout_p, float momentum,
+                            void* stream);
+
 /* ---- fused blocks (inference) ---------------------------------------------------------------
  * fscnn_block_ir_fwd: one stride-1 LinearBottleneck (models/fast_scnn.py:95-115) with its three
  * BatchNorms folded (eval): y = BN_p(W_p * relu(BN_d(dw3x3(relu(BN_e(W_e * x)))))) (+ x when
