@@ -14,8 +14,11 @@ Submodules:
   deploy         EndToEndFastSCNN — the deployment model: raw frames in, probabilities / mask out
   bev            BirdEyeView / centerline — calibration, view parameters and the centreline read
                  from the row table of EndToEndFastSCNN.bird_eye
+  vis            overlay_mask — the lane / class overlay of a frame and a mask on the device
+                 (EndToEndFastSCNN.overlay is the same blend fused behind the backbone)
 """
-__all__ = ["FastSCNN", "get_fast_scnn", "EndToEndFastSCNN", "BirdEyeView", "centerline"]
+__all__ = ["FastSCNN", "get_fast_scnn", "EndToEndFastSCNN", "BirdEyeView", "centerline",
+           "overlay_mask"]
 
 
 def __getattr__(name):
@@ -28,4 +31,7 @@ def __getattr__(name):
     if name in ("BirdEyeView", "centerline"):
         from . import bev
         return getattr(bev, name)
+    if name == "overlay_mask":
+        from . import vis
+        return vis.overlay_mask
     raise AttributeError(name)

@@ -19,6 +19,7 @@ c_ull, c_double = ctypes.c_ulonglong, ctypes.c_double
 P_int, P_ll, P_vp = ctypes.POINTER(c_int), ctypes.POINTER(c_ll), ctypes.POINTER(c_vp)
 P_float = ctypes.POINTER(c_float)
 P_double = ctypes.POINTER(c_double)
+c_uint, P_ubyte = ctypes.c_uint, ctypes.POINTER(ctypes.c_ubyte)
 
 # name -> (restype, argtypes)
 SIGNATURES = {
@@ -78,6 +79,16 @@ SIGNATURES = {
     "fscnn_forward_e2e_bev": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, P_float,
                                       P_float, c_int, c_int, c_int, P_double, c_int, c_int, c_int,
                                       c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "fscnn_overlay_mask": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_int,
+                                   P_ubyte, c_vp, c_int, c_float, c_float, c_float, c_vp, c_vp,
+                                   c_vp]),
+    "fscnn_e2e_overlay": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                  c_int, c_int, c_vp, c_int, c_int, c_int, c_int, P_ubyte, c_uint,
+                                  c_float, c_float, c_float, c_vp, c_vp, c_vp]),
+    "fscnn_forward_e2e_overlay": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, P_float,
+                                          P_float, c_int, c_int, c_int, P_ubyte, c_uint, c_float,
+                                          c_float, c_float, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                          c_vp]),
     "fscnn_seg_metric": (c_int, [c_vp, c_int, c_vp, c_ll, c_int, c_vp, c_vp]),
     "fscnn_forward_aux": (c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp,
                                   c_ull, c_float, c_float, c_vp]),

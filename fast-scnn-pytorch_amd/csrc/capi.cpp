@@ -611,6 +611,110 @@ int fscnn_forward_e2e_bev(const fscnn_plan* plan, const void* x, int x_dtype, in
                          r, ws, stream);
 }
 
+// ---- overlay tail (overlay.hip) --------------------------------------------------------------------
+static int overlay_args(const char* who, const void* frames, int frame_dtype, int channels_last,
+                        int N, int h, int w, float frame_weight, float alpha, float gamma,
+                        unsigned char* out, unsigned char* mask_out, OverlayArgs& o) {
+  if (!frames || !out) {
+    set_error("%s: null frames or out", who);
+    return E_INVALID;
+  }
+  if (h < 2 || w < 2) {
+    set_error("%s: frame %dx%d (sides >= 2)", who, h, w);
+    return E_INVALID;
+  }
+  o.frames = frames; o.frame_dtype = frame_dtype; o.channels_last = channels_last != 0;
+  o.N = N; o.h = h; o.w = w; o.frame_weight = frame_weight; o.alpha = alpha; o.gamma = gamma;
+  o.out = out; o.mask_out = mask_out;
+  return OK;
+}
+
+static int overlay_colors(const char* who, const unsigned char* colors, int C,
+                          unsigned class_mask, OverlayColors& t) {
+  if (!colors || C < 1) {
+    set_error("%s: null colors or C=%d", who, C);
+    return E_INVALID;
+  }
+  t = OverlayColors{};
+  for (int c = 0; c < C && c < OV_CMAX; ++c)
+    for (int k = 0; k < 3; ++k) t.c[c][k] = colors[c * 3 + k];
+  t.on = class_mask;
+  return OK;
+}
+
+int fscnn_overlay_mask(const void* frames, int frame_dtype, int channels_last, int N, int h, int w,
+                       const unsigned char* mask, int Hm, int Wm, const unsigned char* color,
+                       const unsigned char* palette, int P, float frame_weight, float alpha,
+                       float gamma, unsigned char* out, unsigned char* mask_out, void* stream) {
+  OverlayArgs o{};
+  if (int rc = overlay_args("fscnn_overlay_mask", frames, frame_dtype, channels_last, N, h, w,
+                            frame_weight, alpha, gamma, out, mask_out, o))
+    return rc;
+  if (!palette && !color) {
+    set_error("fscnn_overlay_mask: neither a color nor a palette");
+    return E_INVALID;
+  }
+  OverlayColors t{};
+  if (!palette)
+    for (int k = 0; k < 3; ++k) t.c[0][k] = color[k];
+  return overlay_mask(o, mask, Hm, Wm, t, palette, P, S(stream));
+}
+
+int fscnn_e2e_overlay(const void* logits, int dtype, int N, int Hc, int Wc, int C, int ldx,
+                      int base, int h_out, int w_out, int label_scale, const void* frames,
+                      int frame_dtype, int channels_last, int h, int w,
+                      const unsigned char* colors, unsigned class_mask, float frame_weight,
+                      float alpha, float gamma, unsigned char* out, unsigned char* mask_out,
+                      void* stream) {
+  OverlayArgs o{};
+  if (int rc = overlay_args("fscnn_e2e_overlay", frames, frame_dtype, channels_last, N, h, w,
+                            frame_weight, alpha, gamma, out, mask_out, o))
+    return rc;
+  OverlayColors t{};
+  if (int rc = overlay_colors("fscnn_e2e_overlay", colors, C, class_mask, t)) return rc;
+  E2eHeadArgs a{};
+  a.N = N; a.Hl = Hc; a.Wl = Wc; a.C = C; a.base = base; a.Ho = h_out; a.Wo = w_out;
+  a.logits = logits; a.ldx = ldx; a.label_scale = label_scale;
+  return e2e_overlay(a, o, t, dtype, S(stream));
+}
+
+int fscnn_forward_e2e_overlay(const fscnn_plan* plan, const void* x, int x_dtype,
+                              int channels_last, int bgr, int h, int w, const float* mean,
+                              const float* std, int h_out, int w_out, int label_scale,
+                              const unsigned char* colors, unsigned class_mask,
+                              float frame_weight, float alpha, float gamma, unsigned char* out,
+                              unsigned char* mask_out, const float* params, float* running,
+                              long long* nbt, void* ws, void* stream) {
+  if (!plan || !x || !params || !running || !ws) {
+    set_error("fscnn_forward_e2e_overlay: null argument");
+    return E_INVALID;
+  }
+  const Plan& pl = plan->plan;
+  RunArgs r{};
+  if (int rc = overlay_args("fscnn_forward_e2e_overlay", x, x_dtype, channels_last, pl.N, h, w,
+                            frame_weight, alpha, gamma, out, mask_out, r.ov))
+    return rc;
+  if ((const void*)out == x || (const void*)mask_out == x || out == mask_out) {
+    set_error("fscnn_forward_e2e_overlay: the outputs are fresh buffers; aliasing the frames is "
+              "refused");
+    return E_INVALID;
+  }
+  if (x_dtype < DT_F32 || x_dtype > DT_U8) {
+    set_error("fscnn_forward_e2e_overlay: frame dtype %d (0 fp32, 1 bf16, 2 fp16, 3 uint8)",
+              x_dtype);
+    return E_INVALID;
+  }
+  if (int rc = overlay_colors("fscnn_forward_e2e_overlay", colors, pl.net->num_classes,
+                              class_mask, r.ov_colors))
+    return rc;
+  r.P = params; r.R = running; r.NBT = nbt;
+  r.e2e_ho = h_out; r.e2e_wo = w_out; r.e2e_scale = label_scale;
+  return forward_e2e_run("fscnn_forward_e2e_overlay", plan, x, x_dtype, channels_last, bgr, h, w,
+                         mean, std, e2e_overlay_ok(pl.N, pl.net->num_classes, pl.H3, pl.W3, pl.H,
+                                                   h_out, w_out, h, w),
+                         r, ws, stream);
+}
+
 int fscnn_seg_metric(const void* pred, int pred_dtype, const long long* target, long long n,
                      int nclass, long long* counts, void* stream) {
   if ((!pred || !target || !counts) && n > 0) {

@@ -770,6 +770,29 @@ bool e2e_bev_ok(int N, int C, int Hl, int Wl, int base, int Ho, int Wo, int Hb, 
                 int min_width);
 int bev_mask(const BevArgs& a, const uint8_t* mask, hipStream_t st);
 int e2e_bev(const E2eHeadArgs& h, const BevArgs& a, int dtype, hipStream_t st);
+// Overlay tail (overlay.hip): the picture a person looks at -- the frame blended with the lane
+// colour or a per-class palette (include/fastscnn.h: the law).  The label of a frame pixel is the
+// nearest mask pixel: a mask in memory (overlay_mask), or the class e2e_head would pick at that
+// output pixel, evaluated from the low-resolution logits by ee_pixel (e2e_overlay: E2eHeadArgs
+// gives the geometry, label_scale and the logits; its probs / labels are unused).
+constexpr int OV_CMAX = 32;  // = EE_CMAX
+struct OverlayColors {
+  uint8_t c[OV_CMAX][3];  // colour of class id (fused tail); c[0] = the lane colour (overlay_mask)
+  uint32_t on;            // bit id: class id gets its colour (fused tail)
+};
+struct OverlayArgs {
+  const void* frames;  // [N][h][w][3] (channels_last) or [N][3][h][w], frame_dtype 0 .. 3 (DT_U8)
+  int frame_dtype, channels_last, N, h, w;
+  float frame_weight, alpha, gamma;
+  uint8_t* out;       // layout of the frames
+  uint8_t* mask_out;  // [N][h][w] = the label byte of every frame pixel, or null
+};
+bool e2e_overlay_ok(int N, int C, int Hl, int Wl, int base, int Ho, int Wo, int h, int w);
+// palette: DEVICE uint8 [P][3] (palette mode) or null (lane mode: colors.c[0] where the byte != 0)
+int overlay_mask(const OverlayArgs& a, const uint8_t* mask, int Hm, int Wm,
+                 const OverlayColors& colors, const uint8_t* palette, int P, hipStream_t st);
+int e2e_overlay(const E2eHeadArgs& h, const OverlayArgs& a, const OverlayColors& colors, int dtype,
+                hipStream_t st);
 int dropout(const DropArgs& a, int dtype, hipStream_t st);
 // GPU input path: ToTensor + Normalize of uint8 HWC images into NCHW (fp32 / bf16)
 int normalize_u8(const uint8_t* x, int N, int H, int W, const float* mean, const float* std,

@@ -1266,6 +1266,12 @@ struct Exec {
         b.bev = r.bev_mask; b.rows = r.bev_rows;
         return e2e_bev(h, b, dt, r.st);
       }
+      if (r.ov.out) {
+        g_prof_tag = "head (e2e resample + overlay)";
+        OverlayArgs o = r.ov;
+        o.N = N;
+        return e2e_overlay(h, o, r.ov_colors, dt, r.st);
+      }
       return e2e_head(h, dt, r.st);
     }
     if (r.target) {
@@ -1958,7 +1964,7 @@ std::vector<uint64_t> run_key(int kind, int s0, int s1, const RunArgs& r) {
     memcpy(&u, &d, 8);
     return u;
   };
-  return {(uint64_t)kind, (uint64_t)s0, (uint64_t)s1, P(r.x), (uint64_t)r.x_dtype, P(r.out),
+  std::vector<uint64_t> key = {(uint64_t)kind, (uint64_t)s0, (uint64_t)s1, P(r.x), (uint64_t)r.x_dtype, P(r.out),
           (uint64_t)r.out_dtype, P(r.aux_out), P(r.labels), (uint64_t)r.label_u8, P(r.P), P(r.R), P(r.NBT), P(r.G), P(r.ws),
           P(r.bws), P(r.dout), P(r.daux), fbits(r.dropout_p), fbits(r.momentum), P(r.target),
           (uint64_t)r.ignore_index, P(r.loss2), P(r.gloss), P(r.dx), (uint64_t)r.dx_dtype,
@@ -1971,6 +1977,16 @@ std::vector<uint64_t> run_key(int kind, int s0, int s1, const RunArgs& r) {
           P(r.e2e_labels), (uint64_t)r.bev_hb, (uint64_t)r.bev_wb, (uint64_t)r.bev_min_width,
           P(r.bev_mask), P(r.bev_rows), D(r.bev_m[0]), D(r.bev_m[1]), D(r.bev_m[2]), D(r.bev_m[3]),
           D(r.bev_m[4]), D(r.bev_m[5]), D(r.bev_m[6]), D(r.bev_m[7]), D(r.bev_m[8])};
+  if (r.ov.out) {  // the overlay tail's arguments, its colour table (by value) included
+    uint64_t ovc[(sizeof(OverlayColors) + 7) / 8] = {};
+    memcpy(ovc, &r.ov_colors, sizeof(OverlayColors));
+    key.insert(key.end(), {P(r.ov.frames), (uint64_t)r.ov.frame_dtype,
+                           (uint64_t)r.ov.channels_last, (uint64_t)r.ov.h, (uint64_t)r.ov.w,
+                           fbits(r.ov.frame_weight), fbits(r.ov.alpha), fbits(r.ov.gamma),
+                           P(r.ov.out), P(r.ov.mask_out)});
+    key.insert(key.end(), ovc, ovc + sizeof(ovc) / sizeof(ovc[0]));
+  }
+  return key;
 }
 
 template <typename F>

@@ -230,6 +230,11 @@ struct RunArgs {
   double bev_m[9] = {};
   unsigned char* bev_mask = nullptr;
   int* bev_rows = nullptr;
+  // overlay tail (overlay.hip): with ov.out != null the deployment tail is e2e_overlay instead --
+  // the frames ov.frames (ov.N is taken from the plan) blended with the colour of the class at
+  // the nearest pixel of the e2e_ho x e2e_wo output; ov.mask_out (or null) gets argmax * e2e_scale
+  OverlayArgs ov = {};
+  OverlayColors ov_colors = {};
   // backward: gradient of the input image, NCHW [N][3][H][W] in dx_dtype (autograd of x through
   // conv0, models/fast_scnn.py:153), or null
   void* dx = nullptr;

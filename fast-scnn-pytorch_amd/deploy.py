@@ -22,6 +22,11 @@ full-resolution logits nor, for ``predict``, any probability is ever formed.
 mask (``kuruma/vision/transform.py:130-201``, ``path_planning.py:188-293``): from the same
 1/8-resolution logits straight to the bird's-eye mask and the per-row table the centreline is
 read from (``bev.centerline``), without writing the frame-size mask.
+
+``overlay`` is a third tail (``csrc/overlay.hip``) for the picture a person looks at
+(``create_visualization``, ``kuruma/core/preprocessing.py:85-104``): the frame blended with the
+lane colour or a class palette, from the same 1/8-resolution logits and the frame that is already
+in device memory, in one launch.
 """
 import ctypes
 
@@ -296,3 +301,85 @@ class EndToEndFastSCNN(nn.Module):
                                         return_mask)
         object.__setattr__(self, "_last_fused", fused)
         return mask, rows
+
+    # ---- the overlay tail -------------------------------------------------------------------------
+    def _fused_overlay(self, h, w):
+        """Whether ``overlay`` takes the fused tail for ``h x w`` frames.  The fused tail evaluates
+        the class scores once per frame pixel, the two-launch route once per mask pixel, so the
+        fused tail is taken exactly when the frame has no more pixels than the mask: a rule read
+        off the work counts, to be widened only to what profiles/overlay_time.md shows."""
+        return h * w <= int(self.input_size[0]) * int(self.input_size[1])
+
+    def overlay(self, frames, alpha=0.5, color=(0, 255, 0), palette=None, frame_weight=1.0,
+                gamma=0.0, return_mask=False, scale=255, fused=None):
+        """The picture a person looks at: ``frames`` blended with the lane colour, uint8 in the
+        layout of the frames (a fresh buffer), or ``(overlay, mask)`` with ``return_mask=True``.
+
+        The label of a frame pixel is ``predict(frames, scale)`` at the nearest output pixel
+        (``x * W // w``, the ``cv2.INTER_NEAREST`` resize of ``postprocess_matched_resolution``; the
+        identity when the frames have the output's size).  Lane mode (the reference's
+        ``create_visualization``): ``color``, in the frames' own channel order, where the label is
+        not 0.  Palette mode: ``palette`` is a uint8 ``[P, 3]`` tensor or sequence and the class
+        (the argmax itself, whatever ``scale``) picks its row; classes from ``P`` on get no colour.
+        Every pixel is ``frame * frame_weight + colour * alpha + gamma`` in fp32, rounded half to
+        even and saturated (``cv2.addWeighted``; include/fastscnn.h states the law).  ``mask`` is
+        the uint8 ``[N, h, w]`` label of every frame pixel.  One launch after the backbone
+        (``csrc/overlay.hip``): the frame is read once, the overlay written once, and neither a
+        mask nor a probability is formed unless asked for.
+
+        ``fused``: ``None`` picks the route (``_fused_overlay``: the fused tail when the frame has
+        no more pixels than ``input_size``, else ``predict`` followed by ``fscnn_overlay_mask``),
+        ``True`` / ``False`` force one; both give the same bits.  ``_last_fused`` tells which one
+        ran."""
+        from . import vis as _vis
+        frames, N, h, w = self._check(frames)
+        bb, dev = self.backbone, frames.device
+        dt = self._compute_dtype()
+        wo, ho = int(self.input_size[0]), int(self.input_size[1])
+        base = self.base_size
+        table, bits = _vis.class_table(bb.num_classes, scale, color, palette)
+        if fused is None:
+            fused = self._fused_overlay(h, w)
+        rc = E_UNSUPPORTED
+        out = mask = None
+        if fused:
+            with torch.no_grad():
+                nat = bb.native()
+                ar = bb._exec_arena(dev)
+                if ar["P"].device != dev:
+                    raise RuntimeError("EndToEndFastSCNN: frames on %s but parameters on %s"
+                                       % (dev, ar["P"].device))
+                plan, _, _ = nat.plan(N, base, base, _lib.dtype_code(dt), False, dev)
+                lib = _lib.load()
+                need = int(lib.fscnn_e2e_ws_bytes(plan))
+                if need < 0:
+                    _lib.check(need, "fscnn_e2e_ws_bytes")
+                ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+                out = torch.empty(frames.shape, dtype=torch.uint8, device=dev)
+                mask = torch.empty((N, h, w), dtype=torch.uint8, device=dev) if return_mask else None
+                hm, hs = self._norm_host()
+                with torch.cuda.device(dev):
+                    rc = lib.fscnn_forward_e2e_overlay(
+                        plan, _lib.ptr(frames), _FRAME_DTYPES[frames.dtype],
+                        int(self.channels_last), int(self.bgr), h, w, hm, hs, ho, wo,
+                        int(scale) & 255, table, bits, float(frame_weight), float(alpha),
+                        float(gamma), _lib.ptr(out), _lib.ptr(mask), _lib.ptr(ar["P"]),
+                        _lib.ptr(ar["R"]), _lib.ptr(ar["NBT"]), _lib.ptr(ws), _lib.stream_ptr(dev))
+            fused = rc != E_UNSUPPORTED  # nothing was launched: the geometry check comes first
+            if fused:
+                _lib.check(rc, "fscnn_forward_e2e_overlay")
+        if not fused:
+            # by choice, a window too large for LDS, FSCNN_E2E_FUSED=0, more than 32 classes: the
+            # mask, then the blend.  Palette mode blends by class id, so it predicts with scale 1
+            # and scales the returned mask afterwards (uint8 products wrap mod 256, as the label
+            # byte does)
+            by_id = palette is not None
+            labels = self.predict(frames, 1 if by_id else scale)
+            res = _vis.overlay_mask(frames, labels, alpha=alpha, color=color, palette=palette,
+                                    frame_weight=frame_weight, gamma=gamma,
+                                    return_mask=return_mask, channels_last=self.channels_last)
+            out, mask = res if return_mask else (res, None)
+            if by_id and return_mask and (int(scale) & 255) != 1:
+                mask = mask * (int(scale) & 255)
+        object.__setattr__(self, "_last_fused", fused)
+        return (out, mask) if return_mask else out

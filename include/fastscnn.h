@@ -223,6 +223,66 @@ int fscnn_forward_e2e_bev(const fscnn_plan* plan, const void* x, int x_dtype, in
                           int w_out, int label_scale, const double* m, int Hb, int Wb,
                           int min_width, unsigned char* bev, int* rows, const float* params,
                           float* running, long long* nbt, void* ws, void* stream);
+/* Overlay tail of the deployment pipeline: the picture every consumer of the exported model builds
+ * on the host from the frame and the lane mask (create_visualization,
+ * kuruma/core/preprocessing.py:85-104: green where mask > 0, then cv2.addWeighted(frame, 1, green,
+ * alpha, 0); the evaluation scripts blend a per-class colour image at 0.7 / 0.3 or 0.6 / 0.4),
+ * after the nearest-neighbour resize of the mask back to the camera frame
+ * (postprocess_matched_resolution, :53-79).  One launch: the frame is read once and the blended
+ * uint8 frame is written once.  Bit parity with a particular OpenCV build is not claimed; the law
+ * below is what is tested.
+ *
+ * The law.  For output pixel (n, y, x) of an h x w frame and channel k (channels in the frame's
+ * own order; colours are given in that order, no BGR swap), with a mask of Hm x Wm:
+ *   source   sx = (x * Wm) div w, sy = (y * Hm) div h in exact integer division -- cv2.INTER_NEAREST's
+ *            floor(x * Wm / w) taken as a rational; the identity when both sizes agree.  Every
+ *            size is <= 16384.
+ *   label    L = the mask byte at (sy, sx).  From the logits: L = (argmax * label_scale) mod 256,
+ *            evaluated exactly as fscnn_e2e_head evaluates its label at output pixel (sx, sy) of
+ *            an h_out x w_out output (same code: strict >, the lowest class wins ties).
+ *   lane     o_k = color[k] where L != 0, else 0.
+ *   palette  id = the mask byte (mask in memory) or the argmax (logits);
+ *            o_k = palette[id][k] if id < P, else 0; palette: uint8 [P][3], 1 <= P <= 256.
+ *   blend    a = the frame value as fp32 (frames: dtype 0 fp32, 1 bf16, 2 fp16, 3 uint8);
+ *            t = ((a * frame_weight) + (o_k * alpha)) + gamma, each of the four operations rounded
+ *            to fp32 on its own (no fused multiply-add).
+ *   store    out = uint8(min(max(rint(t), 0), 255)), round half to even, NaN -> 0
+ *            (saturate_cast<uchar> of cv2.addWeighted).
+ * out: uint8 in the layout of the frames ([N][h][w][3] with channels_last != 0, else [N][3][h][w]),
+ * a buffer of its own: aliasing the frames is refused (-1).  mask_out: uint8 [N][h][w] = L of every
+ * frame pixel (what postprocess_matched_resolution returns), may be null.  h, w >= 2.
+ *
+ * fscnn_overlay_mask: a uint8 mask [N][Hm][Wm] in device memory.  palette: DEVICE uint8 [P][3]
+ *   (palette mode), or null for lane mode with color = HOST uint8[3].  -2 when a size exceeds the
+ *   limit.
+ * fscnn_e2e_overlay: the low-resolution logits of an inference plan as fscnn_e2e_head takes them.
+ *   Both modes are one form here: colors = HOST uint8 [min(C, 32)][3], the colour of class id, and
+ *   class_mask, whose bit id tells whether class id gets its colour (lane mode: color in every
+ *   row, bit id = ((id * label_scale) mod 256 != 0); palette mode: the palette's rows, bit id =
+ *   (id < P)).  Returns -2 (nothing launched) when C > 32, a size exceeds the limit or the
+ *   low-resolution window of a 64 x 4 tile of frame pixels does not fit the LDS staging (a frame
+ *   much smaller than h_out x w_out).
+ * fscnn_forward_e2e_overlay: front end, backbone and the overlay tail on `stream`; plan, frames
+ *   (x: both the front end's input and the blend's), mean / std and ws (fscnn_e2e_ws_bytes) as
+ *   fscnn_forward_e2e.  Returns -2 before any launch where fscnn_e2e_overlay would and when
+ *   FSCNN_E2E_FUSED=0, like fscnn_forward_e2e. */
+int fscnn_overlay_mask(const void* frames, int frame_dtype, int channels_last, int N, int h, int w,
+                       const unsigned char* mask, int Hm, int Wm, const unsigned char* color,
+                       const unsigned char* palette, int P, float frame_weight, float alpha,
+                       float gamma, unsigned char* out, unsigned char* mask_out, void* stream);
+int fscnn_e2e_overlay(const void* logits, int dtype, int N, int Hc, int Wc, int C, int ldx,
+                      int base, int h_out, int w_out, int label_scale, const void* frames,
+                      int frame_dtype, int channels_last, int h, int w,
+                      const unsigned char* colors, unsigned class_mask, float frame_weight,
+                      float alpha, float gamma, unsigned char* out, unsigned char* mask_out,
+                      void* stream);
+int fscnn_forward_e2e_overlay(const fscnn_plan* plan, const void* x, int x_dtype,
+                              int channels_last, int bgr, int h, int w, const float* mean,
+                              const float* std, int h_out, int w_out, int label_scale,
+                              const unsigned char* colors, unsigned class_mask,
+                              float frame_weight, float alpha, float gamma, unsigned char* out,
+                              unsigned char* mask_out, const float* params, float* running,
+                              long long* nbt, void* ws, void* stream);
 
 /* SegmentationMetric counters (utils/metric.py:73-105, batch_pix_accuracy +
  * batch_intersection_union) of n predictions (pred_dtype 0 int64, 1 uint8) against int64 labels,
