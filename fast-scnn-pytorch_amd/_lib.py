@@ -164,6 +164,30 @@ SIGNATURES = {
                                    c_vp, c_int, c_vp]),
     "fscnn_pyramid_pool_bwd": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_int,
                                        c_int, c_vp]),
+    # train-only kernels in the executor's form (tests/test_gpu_train_kernels.py)
+    "fscnn_bn_apply": (c_int, [c_ll, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp,
+                               c_int, c_int, c_vp, c_int, c_int, c_vp]),
+    "fscnn_bn_bwd": (c_int, [c_ll, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
+                             c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                             c_vp, c_vp, c_vp, c_vp, c_int, P_int, P_int, c_vp]),
+    "fscnn_ppm_branches_ok": (c_int, [c_int, c_int, c_int]),
+    "fscnn_ppm_branches_fwd": (c_int, [c_int, P_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                       c_vp, c_float, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp,
+                                       c_int, c_vp]),
+    "fscnn_ppm_branches_bwd": (c_int, [c_int, P_int, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp,
+                                       c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int,
+                                       c_vp]),
+    "fscnn_ppm_up_fwd": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp]),
+    "fscnn_ppm_up_bwd": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
+    "fscnn_dropout": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_ull, c_vp, c_ull,
+                              c_float, c_vp, c_vp, c_vp, c_int, c_vp]),
+    "fscnn_dw3x3_parts": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "fscnn_dw3x3_fwd_train": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp,
+                                      c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                      c_float, c_vp, c_vp, c_vp, c_vp, P_int, c_vp]),
+    "fscnn_dw3x3_dgrad_bn": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp,
+                                     c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp,
+                                     c_vp, c_vp, P_int, c_vp]),
     "fscnn_block_ir_s2_fwd": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                       c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                       c_int, c_vp]),

@@ -1207,6 +1207,387 @@ int fscnn_pyramid_pool_bwd(const void* dpooled, int dtype, int N, int H, int W, 
   return pyramid_pool_bwd(a, dtype, S(stream));
 }
 
+// ---- the kernels only a train step runs, in the executor's form (tests/test_gpu_train_kernels.py).
+// Each wrapper fills the *Args struct as net.cpp does and refuses null / inconsistent arguments
+// before anything is launched; none has arithmetic of its own.
+static bool dt_ok(int dtype) { return dtype >= DT_F32 && dtype <= DT_F16; }
+static int vec_w(int dtype) { return dtype == DT_F32 ? 4 : 8; }  // elements per 16-B vector
+// a row stride the 16-B vector loads take: >= C and a multiple of the vector width
+static bool ld_ok(int ld, int C, int V) { return ld >= C && ld % V == 0; }
+
+int fscnn_bn_apply(long long M, int C, const void* z, int ldz, const float* scale,
+                   const float* shift, const void* z2, int ldz2, const float* scale2,
+                   const float* shift2, const void* res, int ldres, int relu, void* y, int ldy,
+                   int dtype, void* stream) {
+  if (!z || !scale || !shift || !y || (z2 && (!scale2 || !shift2))) {
+    set_error("fscnn_bn_apply: null argument");
+    return E_INVALID;
+  }
+  if (!dt_ok(dtype)) {
+    set_error("fscnn_bn_apply: dtype %d", dtype);
+    return E_INVALID;
+  }
+  const int V = vec_w(dtype);
+  if (M < 1 || C < 1 || C % V || !ld_ok(ldz, C, V) || !ld_ok(ldy, C, V) ||
+      (z2 && !ld_ok(ldz2, C, V)) || (res && !ld_ok(ldres, C, V)) ||
+      M * (C / V) >= (1LL << 31)) {
+    set_error("fscnn_bn_apply: M=%lld C=%d ldz=%d ldz2=%d ldres=%d ldy=%d (C and every row stride "
+              "a multiple of %d, strides >= C)", M, C, ldz, ldz2, ldres, ldy, V);
+    return E_INVALID;
+  }
+  // net.cpp Exec::apply (plain / residual) and the FFM's two-branch form
+  BnApplyArgs a{};
+  a.M = M; a.C = C;
+  a.z = z; a.ldz = ldz; a.scale = scale; a.shift = shift;
+  a.z2 = z2; a.ldz2 = ldz2; a.scale2 = scale2; a.shift2 = shift2;
+  a.res = res; a.ldres = ldres;
+  a.relu = relu;
+  a.y = y; a.ldy = ldy;
+  return bn_apply(a, dtype, S(stream));
+}
+
+int fscnn_bn_bwd(long long M, int C, const void* dy, int lddy, const void* mask, int ldmask,
+                 const void* z, const float* mean, const float* invstd, const float* scale,
+                 const float* shift, int relu_mode, int frozen, const void* z2,
+                 const float* mean2, const float* invstd2, const float* scale2, float* part,
+                 unsigned* counters, void* dz, void* dz2, float* dgamma, float* dbeta,
+                 float* dgamma2, float* dbeta2, float* coef, int dtype, int* P_out,
+                 int* rows_per_block_out, void* stream) {
+  if (!dy || !z || !mean || !invstd || !scale || !part || !counters || !dz || !dgamma || !dbeta ||
+      !coef) {
+    set_error("fscnn_bn_bwd: null argument");
+    return E_INVALID;
+  }
+  if (!dt_ok(dtype) || relu_mode < 0 || relu_mode > 2 || frozen < 0 || frozen > 2) {
+    set_error("fscnn_bn_bwd: dtype %d / relu_mode %d / frozen %d", dtype, relu_mode, frozen);
+    return E_INVALID;
+  }
+  const int V = vec_w(dtype);
+  if (M < 1 || C < 1 || C % V || !ld_ok(lddy, C, V)) {
+    set_error("fscnn_bn_bwd: M=%lld C=%d lddy=%d (C and lddy a multiple of %d, lddy >= C)", M, C,
+              lddy, V);
+    return E_INVALID;
+  }
+  if ((relu_mode == 1) != (mask != nullptr) || (mask && !ld_ok(ldmask, C, V)) ||
+      (relu_mode == 2 && !shift)) {
+    set_error("fscnn_bn_bwd: relu_mode %d needs %s (ldmask=%d)", relu_mode,
+              relu_mode == 1 ? "a mask tensor" : relu_mode == 2 ? "the forward shift and no mask"
+                                                                : "no mask", ldmask);
+    return E_INVALID;
+  }
+  const bool pair = z2 != nullptr;
+  if (pair && (relu_mode != 1 || frozen == 2 || !mean2 || !invstd2 || !scale2 || !dz2 ||
+               !dgamma2 || !dbeta2 || 4 * C > 2048)) {
+    set_error("fscnn_bn_bwd: a paired BN needs the mask mode (relu_mode 1), its own statistics, "
+              "dz2 / dgamma2 / dbeta2, coefficients passed to the apply and C <= 512");
+    return E_INVALID;
+  }
+  hipStream_t st = S(stream);
+  int rpb;
+  const int P = bn_bwd_parts(M, C, dtype, &rpb);
+  if (P_out) *P_out = P;
+  if (rows_per_block_out) *rows_per_block_out = rpb;
+  const double count = frozen ? BN_FROZEN_COUNT : (double)M;
+  // net.cpp Exec::bn_bwd_stats + bn_bwd, or bn_bwd_pair: reduce, finish(es), apply
+  BnBwdArgs b{};
+  b.M = M; b.C = C;
+  b.dy = dy; b.lddy = lddy; b.mask = mask; b.ldmask = ldmask;
+  b.z = z; b.ldz = C;
+  b.mean = mean; b.invstd = invstd; b.scale = scale; b.shift = shift;
+  b.relu_z = relu_mode == 2;
+  b.part = part;
+  float* coef2 = coef + 2 * C;
+  if (pair) {
+    b.z2 = z2; b.mean2 = mean2; b.invstd2 = invstd2; b.scale2 = scale2;
+    b.part2 = part + (size_t)P * 2 * C;
+  }
+  int rc = bn_bwd_reduce(b, dtype, st);
+  if (rc) return rc;
+  rc = bn_bwd_finalize(b.part, P, C, count, dgamma, dbeta, coef, st, counters, BnBwdTab());
+  if (rc) return rc;
+  if (pair) {
+    rc = bn_bwd_finalize(b.part2, P, C, count, dgamma2, dbeta2, coef2, st, counters, BnBwdTab());
+    if (rc) return rc;
+    b.coef2 = coef2; b.dz2 = dz2;
+  }
+  b.coef = frozen == 2 ? nullptr : coef;
+  b.dz = dz; b.lddz = C;
+  return bn_bwd_apply(b, dtype, st);
+}
+
+int fscnn_ppm_branches_ok(int maxM, int K, int dtype) {
+  return ppm_branches_ok(maxM, K, dtype) ? 1 : 0;
+}
+
+// the branch layout of both PPM calls: rows packed branch after branch (the executor's bin-major
+// pooled tensor), per-branch tables [nb][32]
+static int ppm_rows(const char* who, int nb, const int* M, int K, int dtype, int off[5]) {
+  if (nb < 1 || nb > 4 || !M) {
+    set_error("%s: nb=%d (1 .. 4 branches, row counts in M)", who, nb);
+    return E_INVALID;
+  }
+  if (!dt_ok(dtype)) {
+    set_error("%s: dtype %d", who, dtype);
+    return E_INVALID;
+  }
+  int maxM = 0;
+  off[0] = 0;
+  for (int i = 0; i < nb; ++i) {
+    if (M[i] < 1) {
+      set_error("%s: branch %d has M=%d rows", who, i, M[i]);
+      return E_INVALID;
+    }
+    maxM = std::max(maxM, M[i]);
+    off[i + 1] = off[i] + M[i];
+  }
+  if (!ppm_branches_ok(maxM, K, dtype)) {
+    set_error("%s: M=%d K=%d dtype=%d not supported (M <= 512, K a multiple of 8)", who, maxM, K,
+              dtype);
+    return E_UNSUPPORTED;
+  }
+  return OK;
+}
+
+int fscnn_ppm_branches_fwd(int nb, const int* M, int K, const void* x, const void* w,
+                           const float* gamma, const float* beta, float* rmean, float* rvar,
+                           long long* nbt, float momentum, void* z, void* y, int ldy, float* mean,
+                           float* invstd, float* scale, float* shift, int dtype, void* stream) {
+  if (!x || !w || !gamma || !beta || !rmean || !rvar || !z || !y || !mean || !invstd || !scale ||
+      !shift) {
+    set_error("fscnn_ppm_branches_fwd: null argument");
+    return E_INVALID;
+  }
+  int off[5];
+  const int rc = ppm_rows("fscnn_ppm_branches_fwd", nb, M, K, dtype, off);
+  if (rc) return rc;
+  if (ldy < 32) {
+    set_error("fscnn_ppm_branches_fwd: ldy=%d < 32", ldy);
+    return E_INVALID;
+  }
+  const size_t E = dtype == DT_F32 ? 4 : 2;
+  // net.cpp forward, "global_feature_extractor.ppm.conv1-4" (fin_args per branch)
+  PpmFwdArgs f{};
+  f.nb = nb; f.K = K; f.C = 32;
+  for (int i = 0; i < nb; ++i) {
+    PpmBranchFwd& b = f.b[i];
+    b.f.gamma = gamma + 32 * i; b.f.beta = beta + 32 * i;
+    b.f.rmean = rmean + 32 * i; b.f.rvar = rvar + 32 * i;
+    b.f.nbt = nbt ? nbt + i : nullptr;
+    b.f.momentum = momentum;
+    b.f.mean = mean + 32 * i; b.f.invstd = invstd + 32 * i;
+    b.f.scale = scale + 32 * i; b.f.shift = shift + 32 * i;
+    b.f.C = 32;
+    b.x = (const char*)x + (size_t)off[i] * K * E;
+    b.w = (const char*)w + (size_t)i * 32 * K * E;
+    b.z = (char*)z + (size_t)off[i] * 32 * E;
+    b.y = (char*)y + (size_t)off[i] * ldy * E;
+    b.ldy = ldy; b.M = M[i];
+  }
+  return ppm_branches_fwd(f, dtype, S(stream));
+}
+
+int fscnn_ppm_branches_bwd(int nb, const int* M, int K, const void* dy, int lddy, const void* y,
+                           int ldy, const void* z, const float* mean, const float* invstd,
+                           const float* scale, const float* gamma, const void* x, const void* w,
+                           float* dgamma, float* dbeta, float* dw, void* dx, int dtype,
+                           void* stream) {
+  if (!dy || !y || !z || !mean || !invstd || !scale || !gamma || !x || !w || !dgamma || !dbeta ||
+      !dw || !dx) {
+    set_error("fscnn_ppm_branches_bwd: null argument");
+    return E_INVALID;
+  }
+  int off[5];
+  const int rc = ppm_rows("fscnn_ppm_branches_bwd", nb, M, K, dtype, off);
+  if (rc) return rc;
+  if (lddy < 32 || ldy < 32) {
+    set_error("fscnn_ppm_branches_bwd: lddy=%d ldy=%d < 32", lddy, ldy);
+    return E_INVALID;
+  }
+  const size_t E = dtype == DT_F32 ? 4 : 2;
+  // net.cpp backward_head, "global_feature_extractor.ppm.conv1-4 (backward)"
+  PpmBwdArgs f{};
+  f.nb = nb; f.K = K; f.C = 32;
+  for (int i = 0; i < nb; ++i) {
+    PpmBranchBwd& b = f.b[i];
+    b.dy = (const char*)dy + (size_t)off[i] * lddy * E; b.lddy = lddy;
+    b.y = (const char*)y + (size_t)off[i] * ldy * E; b.ldy = ldy;
+    b.z = (const char*)z + (size_t)off[i] * 32 * E;
+    b.mean = mean + 32 * i; b.invstd = invstd + 32 * i; b.scale = scale + 32 * i;
+    b.gamma = gamma + 32 * i;
+    b.x = (const char*)x + (size_t)off[i] * K * E;
+    b.w = (const char*)w + (size_t)i * 32 * K * E;
+    b.dgamma = dgamma + 32 * i; b.dbeta = dbeta + 32 * i;
+    b.dw = dw + (size_t)i * 32 * K;
+    b.dx = (char*)dx + (size_t)off[i] * K * E;
+    b.M = M[i];
+  }
+  return ppm_branches_bwd(f, dtype, S(stream));
+}
+
+// the concat slice of both PPM upsample calls: 4 levels x 32 channels at channel offset coff
+static int ppm_up_check(const char* who, int dtype, int N, int H, int W, int ldy, int coff) {
+  if (!dt_ok(dtype)) {
+    set_error("%s: dtype %d", who, dtype);
+    return E_INVALID;
+  }
+  const int V = vec_w(dtype);
+  if (N < 1 || H < 1 || W < 1 || coff < 0 || coff % V || ldy % V || ldy < coff + 128) {
+    set_error("%s: N=%d H=%d W=%d ldy=%d coff=%d (128 channels at coff within ldy, both a "
+              "multiple of %d)", who, N, H, W, ldy, coff, V);
+    return E_INVALID;
+  }
+  return OK;
+}
+
+int fscnn_ppm_up_fwd(const void* feats, int dtype, int N, int H, int W, void* y, int ldy, int coff,
+                     void* stream) {
+  if (!feats || !y) {
+    set_error("fscnn_ppm_up_fwd: null argument");
+    return E_INVALID;
+  }
+  const int rc = ppm_up_check("fscnn_ppm_up_fwd", dtype, N, H, W, ldy, coff);
+  if (rc) return rc;
+  PpmUpArgs u{};
+  u.N = N; u.H = H; u.W = W; u.CF = 32; u.feats = feats;
+  u.y = y; u.ldy = ldy; u.coff = coff;
+  return ppm_up_fwd(u, dtype, S(stream));
+}
+
+int fscnn_ppm_up_bwd(const void* dy, int dtype, int N, int H, int W, int ldy, int coff,
+                     void* dfeats, void* stream) {
+  if (!dy || !dfeats) {
+    set_error("fscnn_ppm_up_bwd: null argument");
+    return E_INVALID;
+  }
+  const int rc = ppm_up_check("fscnn_ppm_up_bwd", dtype, N, H, W, ldy, coff);
+  if (rc) return rc;
+  if (H > 80 || N > 65535) {
+    set_error("fscnn_ppm_up_bwd: H=%d N=%d (H <= 80: the row sums of a level stay in LDS)", H, N);
+    return E_UNSUPPORTED;
+  }
+  PpmUpArgs u{};
+  u.N = N; u.H = H; u.W = W; u.CF = 32; u.feats = nullptr;
+  u.y = const_cast<void*>(dy); u.ldy = ldy; u.coff = coff;
+  return ppm_up_bwd(u, dfeats, dtype, S(stream));
+}
+
+int fscnn_dropout(const void* x, int ldx, int dtype, int N, int H, int W, int C,
+                  unsigned long long seed, const unsigned long long* seed_slot,
+                  unsigned long long seed_add, float p, const float* x_scale,
+                  const float* x_shift, void* y, int ldy, void* stream) {
+  if (!x || !y || ((x_scale != nullptr) != (x_shift != nullptr))) {
+    set_error("fscnn_dropout: null argument (x_scale and x_shift come together)");
+    return E_INVALID;
+  }
+  if (!dt_ok(dtype) || !(p >= 0.f && p < 1.f)) {
+    set_error("fscnn_dropout: dtype %d / p %g", dtype, (double)p);
+    return E_INVALID;
+  }
+  const int V = vec_w(dtype);
+  if (N < 1 || H < 1 || W < 1 || C < 1 || C % V || !ld_ok(ldx, C, V) || !ld_ok(ldy, C, V) ||
+      (long long)N * H * W * (C / V) >= (1LL << 31)) {
+    set_error("fscnn_dropout: N=%d H=%d W=%d C=%d ldx=%d ldy=%d (C, ldx and ldy a multiple of "
+              "%d, strides >= C)", N, H, W, C, ldx, ldy, V);
+    return E_INVALID;
+  }
+  // net.cpp forward (classifier Dropout, lazy BN form) / backward_head / forward_aux (seed_add 1)
+  DropArgs d{};
+  d.N = N; d.H = H; d.W = W; d.C = C; d.x = x; d.ldx = ldx;
+  d.x_scale = x_scale; d.x_shift = x_shift;
+  d.y = y; d.ldy = ldy; d.seed = seed; d.p = p; d.seed_add = seed_add;
+  d.seed_ptr = reinterpret_cast<const uint64_t*>(seed_slot);
+  return dropout(d, dtype, S(stream));
+}
+
+// geometry shared by the depthwise train wrappers
+static int dw_train_check(const char* who, int dtype, int N, int H, int W, int C, int stride) {
+  if (!dt_ok(dtype)) {
+    set_error("%s: dtype %d", who, dtype);
+    return E_INVALID;
+  }
+  const int V = vec_w(dtype);
+  if (N < 1 || H < 1 || W < 1 || C < 1 || C % V || (stride != 1 && stride != 2)) {
+    set_error("%s: N=%d H=%d W=%d C=%d stride=%d (C a multiple of %d, stride 1 or 2)", who, N, H,
+              W, C, stride, V);
+    return E_INVALID;
+  }
+  return OK;
+}
+
+int fscnn_dw3x3_parts(int N, int H, int W, int C, int stride, int dtype, int dgrad) {
+  if (dw_train_check("fscnn_dw3x3_parts", dtype, N, H, W, C, stride)) return -1;
+  if (dgrad) return dw_dgrad_parts(N, H, W, C, dtype, stride);
+  return dw_parts(N, (H - 1) / stride + 1, (W - 1) / stride + 1, C, dtype, stride);
+}
+
+int fscnn_dw3x3_fwd_train(const void* x, int dtype, int N, int H, int W, int C, int stride,
+                          const float* w, const float* in_scale, const float* in_shift, void* z,
+                          float* part, unsigned* counters, double* tsum, const float* gamma,
+                          const float* beta, float* rmean, float* rvar, long long* nbt,
+                          float momentum, float* mean, float* invstd, float* scale, float* shift,
+                          int* in_kernel, void* stream) {
+  if (!x || !w || !z || !part || !counters || !tsum || !gamma || !beta || !rmean || !rvar ||
+      !mean || !invstd || !scale || !shift || ((in_scale != nullptr) != (in_shift != nullptr))) {
+    set_error("fscnn_dw3x3_fwd_train: null argument (in_scale and in_shift come together)");
+    return E_INVALID;
+  }
+  const int rc = dw_train_check("fscnn_dw3x3_fwd_train", dtype, N, H, W, C, stride);
+  if (rc) return rc;
+  // net.cpp Exec::dw, train form (fin_args)
+  DwArgs d{};
+  d.N = N; d.H = H; d.W = W; d.C = C; d.stride = stride;
+  d.Ho = (H - 1) / stride + 1; d.Wo = (W - 1) / stride + 1;
+  d.x = x; d.w = w; d.in_scale = in_scale; d.in_shift = in_shift;
+  d.relu = 0; d.y = z;
+  d.part = part;
+  d.tail.counters = counters;
+  d.tail.tsum = tsum;
+  BnFinalizeArgs& f = d.tail.fwd;
+  f.part = part; f.C = C;
+  f.P = dw_parts(N, d.Ho, d.Wo, C, dtype, stride);
+  f.gamma = gamma; f.beta = beta; f.rmean = rmean; f.rvar = rvar; f.nbt = nbt;
+  f.momentum = momentum;
+  f.mean = mean; f.invstd = invstd; f.scale = scale; f.shift = shift;
+  f.counters = counters;
+  int P;
+  if (in_kernel) *in_kernel = dw_fwd_tail_ink(d, dtype, &P);
+  return dw_fwd(d, dtype, S(stream));
+}
+
+int fscnn_dw3x3_dgrad_bn(const void* dy, int dtype, int N, int H, int W, int C, int stride,
+                         const float* w, void* dx, const void* z, const float* mean,
+                         const float* invstd, const float* scale, const float* shift,
+                         int relu_mode, float* part, unsigned* counters, double* tsum,
+                         float* dgamma, float* dbeta, float* coef, int* in_kernel, void* stream) {
+  if (!dy || !w || !dx || !z || !mean || !invstd || !part || !counters || !tsum || !dgamma ||
+      !dbeta || !coef) {
+    set_error("fscnn_dw3x3_dgrad_bn: null argument");
+    return E_INVALID;
+  }
+  const int rc = dw_train_check("fscnn_dw3x3_dgrad_bn", dtype, N, H, W, C, stride);
+  if (rc) return rc;
+  if ((relu_mode != 0 && relu_mode != 2) || (relu_mode == 2 && (!scale || !shift))) {
+    set_error("fscnn_dw3x3_dgrad_bn: relu_mode %d (0, or 2 with the forward scale and shift)",
+              relu_mode);
+    return E_INVALID;
+  }
+  // net.cpp Exec::dw_bwd with a BN target (bt)
+  DwBwdArgs d{};
+  d.N = N; d.H = H; d.W = W; d.C = C; d.stride = stride;
+  d.Ho = (H - 1) / stride + 1; d.Wo = (W - 1) / stride + 1;
+  d.dy = dy; d.w = w; d.dx = dx;
+  d.bs.part = part; d.bs.z = z;
+  d.bs.mean = mean; d.bs.invstd = invstd; d.bs.scale = scale; d.bs.shift = shift;
+  d.bs.mode = relu_mode;
+  d.tail.counters = counters;
+  d.tail.tsum = tsum;
+  d.tail.count = (double)N * H * W;
+  d.tail.dgamma = dgamma; d.tail.dbeta = dbeta; d.tail.coef = coef;
+  int P;
+  if (in_kernel) *in_kernel = dw_dgrad_tail_ink(d, dtype, &P);
+  return dw_dgrad(d, dtype, S(stream));
+}
+
 int fscnn_block_ir_fwd(const void* x, int ldx, int dtype, int N, int H, int W, int cin, int expand,
                        int cout, const void* w_expand, const float* w_dw, const void* w_project,
                        const float* scale_e, const float* shift_e, const float* scale_d,

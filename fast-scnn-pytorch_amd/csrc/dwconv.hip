@@ -407,6 +407,15 @@ static int dw_launch_fwd(const DwArgs& a, int dtype, hipStream_t st) {
   return check_launch(FLIP ? "dw_dgrad" : "dw_fwd");
 }
 
+// whether the tile launch over a's output map (P records, returned) finishes the BN of a.tail in
+// its last workgroups: the records and channel chunks fit the counters and the team sums exist
+int dw_fwd_tail_ink(const DwArgs& a, int dtype, int* P) {
+  int cbv;
+  const dim3 g = dw_grid(a.N, a.Ho, a.Wo, a.C, dtype == DT_F32 ? 4 : 8, a.stride, cbv);
+  *P = (int)(g.y * g.z);
+  return a.tail.counters && a.tail.tsum && a.C <= TAIL_CMAX && tail_fits(*P, (int)g.x);
+}
+
 int dw_fwd(const DwArgs& a, int dtype, hipStream_t st) {
   int V = dtype == DT_F32 ? 4 : 8;
   if (a.C % V || (a.stride != 1 && a.stride != 2) || a.Ho != (a.H - 1) / a.stride + 1 ||
@@ -425,12 +434,8 @@ int dw_fwd(const DwArgs& a, int dtype, hipStream_t st) {
   }
   DwArgs b = a;
   int P = 0;
-  if (a.part && a.tail.counters) {  // BN finish: in the kernel when the records fit its counters
-    int cbv;
-    const dim3 g = dw_grid(a.N, a.Ho, a.Wo, a.C, V, a.stride, cbv);
-    P = (int)(g.y * g.z);
-    b.tail_ink = a.tail.tsum && a.C <= TAIL_CMAX && tail_fits(P, (int)g.x);
-  }
+  // BN finish: in the kernel when the records fit its counters
+  if (a.part && a.tail.counters) b.tail_ink = dw_fwd_tail_ink(a, dtype, &P);
   const int rc = a.in_scale ? dw_launch_fwd<false, true>(b, dtype, st) : dw_launch_fwd<false, false>(b, dtype, st);
   if (rc || !a.part || !a.tail.counters || b.tail_ink) return rc;
   ps.reset();
@@ -624,6 +629,16 @@ static int dwd2_rpw(int gy, int NB) {
   return rpw;
 }
 
+// the same for the dgrad's BnBwdPart records (P returned for stride 1): stride 1 is the flipped
+// forward over the dx map; stride 2 always finishes in its own fold+finalize launch
+int dw_dgrad_tail_ink(const DwBwdArgs& a, int dtype, int* P) {
+  if (a.stride != 1) return 0;
+  DwArgs f{};
+  f.N = a.N; f.Ho = a.H; f.Wo = a.W; f.C = a.C; f.stride = 1;
+  f.tail = a.tail;
+  return dw_fwd_tail_ink(f, dtype, P);
+}
+
 int dw_dgrad(const DwBwdArgs& a, int dtype, hipStream_t st) {
   const int V = dtype == DT_F32 ? 4 : 8;
   const double E = dtype == DT_F32 ? 4.0 : 2.0;
@@ -653,12 +668,8 @@ int dw_dgrad(const DwBwdArgs& a, int dtype, hipStream_t st) {
     f.x = a.dy; f.w = a.w; f.y = a.dx;
     f.bs = a.bs;
     if (fin) {
-      int cbv;
-      const dim3 g = dw_grid(a.N, a.H, a.W, a.C, V, 1, cbv);
-      P = (int)(g.y * g.z);
-      ink = a.tail.tsum && a.C <= TAIL_CMAX && tail_fits(P, (int)g.x);
       f.tail = a.tail;
-      f.tail_ink = ink;
+      f.tail_ink = ink = dw_dgrad_tail_ink(a, dtype, &P);
     }
     rc = br ? dw_launch_fwd<true, false, true>(f, dtype, st) : dw_launch_fwd<true, false>(f, dtype, st);
   } else {

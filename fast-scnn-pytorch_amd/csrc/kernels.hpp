@@ -613,6 +613,10 @@ int dw_parts(int N, int Ho, int Wo, int C, int dtype, int stride);
 int dw_fwd(const DwArgs& a, int dtype, hipStream_t st);
 int dw_dgrad(const DwBwdArgs& a, int dtype, hipStream_t st);
 int dw_dgrad_parts(int N, int H, int W, int C, int dtype, int stride);  // BnBwdPart records
+// whether dw_fwd / dw_dgrad finish the BN of a.tail inside the kernel (else: their own finalize
+// launch); *P: the record count of the tile launch
+int dw_fwd_tail_ink(const DwArgs& a, int dtype, int* P);
+int dw_dgrad_tail_ink(const DwBwdArgs& a, int dtype, int* P);
 int dw_wgrad_parts(int N, int Ho, int Wo, int C, int dtype, int stride);
 int dw_wgrad(const DwBwdArgs& a, int dtype, hipStream_t st);
 int dw_wgrad_reduce(float* slab, int P, int C, float* dw, hipStream_t st);

@@ -421,6 +421,9 @@ __global__ __launch_bounds__(PPM_T) void ppm_bwd_kernel(PpmBwdArgs a) {
   }
   const double c0 = s1 / (double)M, c1 = s2 / (double)M;
   const double scale = (double)b.gamma[n] * istd;
+  // (fp16: hipcc merges the (float) below and the fp16 rounding into one fp64 -> fp16 conversion,
+  //  so dz is the correctly rounded fp64 value; bf16 rounds through fp32.  The two agree except
+  //  where the fp32 value is an exact tie of the storage type: tests/test_gpu_train_kernels.py)
 #pragma unroll
   for (int i = 0; i < RMAX; ++i) {
     if (i >= nr) continue;

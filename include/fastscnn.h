@@ -695,6 +695,91 @@ int fscnn_pyramid_pool_fwd(const void* x, int dtype, int N, int H, int W, int C,
 int fscnn_pyramid_pool_bwd(const void* dpooled, int dtype, int N, int H, int W, int C, void* dx,
                            int lddx, int accumulate, void* stream);
 
+/* ---- kernels that only a train step runs, in the executor's form (tests/test_gpu_train_kernels.py).
+ * Every call refuses null or inconsistent arguments with a non-zero code before anything is
+ * launched.  V below is the 16-byte vector width: 4 elements (fp32) or 8 (bf16 / fp16); C and
+ * every row stride must be a multiple of it. */
+/* y[M][C] (ldy) = act(z*scale + shift [+ z2*scale2 + shift2] [+ res]), act = ReLU when relu;
+ * z2 (the FFM's second branch) and res (a shortcut) are optional. */
+int fscnn_bn_apply(long long M, int C, const void* z, int ldz, const float* scale,
+                   const float* shift, const void* z2, int ldz2, const float* scale2,
+                   const float* shift2, const void* res, int ldres, int relu, void* y, int ldy,
+                   int dtype, void* stream);
+/* BatchNorm backward of dy[M][C] (lddy) through a BN with input z[M][C] (contiguous): the reduce,
+ * finish and apply launches in the executor's order.
+ *   dy_r = dy * mask;  relu_mode 0: no mask, 1: mask[M][C] (ldmask) > 0 (the saved ReLU output),
+ *   2: z*scale + shift > 0 recomputed (mask null);
+ *   dbeta = sum dy_r, dgamma = sum dy_r*xhat, xhat = (z - mean)*invstd;
+ *   coef[0..C) = dbeta / M, coef[C..2C) = dgamma / M;  dz[M][C] = scale*(dy_r - coef0 - xhat*coef1).
+ * frozen 1: a BN normalised with running statistics (the coefficients are zero, dz = scale*dy_r),
+ * as eval-mode autograd runs it; frozen 2: the same with the apply kernel's own no-coefficient
+ * form.  z2 (optional, relu_mode 1 only, C <= 512): a second BN on the same dy and mask (the
+ * FFM), with mean2 / invstd2 / scale2, outputs dz2 / dgamma2 / dbeta2 and coef[2C..4C).
+ * Scratch: part >= 2048*2*C floats (twice that when paired), counters 512 zeroed uint32 (left
+ * zero).  *P / *rows_per_block (nullable): the reduce's record count and rows per record. */
+int fscnn_bn_bwd(long long M, int C, const void* dy, int lddy, const void* mask, int ldmask,
+                 const void* z, const float* mean, const float* invstd, const float* scale,
+                 const float* shift, int relu_mode, int frozen, const void* z2,
+                 const float* mean2, const float* invstd2, const float* scale2, float* part,
+                 unsigned* counters, void* dz, void* dz2, float* dgamma, float* dbeta,
+                 float* dgamma2, float* dbeta2, float* coef, int dtype, int* P,
+                 int* rows_per_block, void* stream);
+/* The PyramidPooling branch convs (1x1, K -> 32) + BN + ReLU of a train step, one launch each
+ * way.  nb <= 4 branches of M[i] <= 512 rows (host array), packed branch after branch: x [sum M][K],
+ * w [nb][32][K] (storage type), z [sum M][32], y [sum M][ldy]; gamma .. shift, dgamma, dbeta are
+ * [nb][32], nbt [nb] (nullable), dw [nb][32][K] fp32, dx [sum M][K].  The forward writes the
+ * batch statistics tables and updates the running ones; the backward recomputes the batch
+ * statistics in fp64 from z and takes the ReLU mask from y > 0.  fscnn_ppm_branches_ok: whether
+ * the launch takes branches of up to maxM rows (else both calls return an error). */
+int fscnn_ppm_branches_ok(int maxM, int K, int dtype);
+int fscnn_ppm_branches_fwd(int nb, const int* M, int K, const void* x, const void* w,
+                           const float* gamma, const float* beta, float* rmean, float* rvar,
+                           long long* nbt, float momentum, void* z, void* y, int ldy, float* mean,
+                           float* invstd, float* scale, float* shift, int dtype, void* stream);
+int fscnn_ppm_branches_bwd(int nb, const int* M, int K, const void* dy, int lddy, const void* y,
+                           int ldy, const void* z, const float* mean, const float* invstd,
+                           const float* scale, const float* gamma, const void* x, const void* w,
+                           float* dgamma, float* dbeta, float* dw, void* dx, int dtype,
+                           void* stream);
+/* Bilinear (align_corners) upsample of the four PPM levels, feats bin-major [50][N][32], into
+ * channels [coff, coff + 128) of the NHWC concat tensor y [N][H][W][ldy], and its backward from
+ * the same slice of dy (H <= 80) to dfeats [50][N][32]. */
+int fscnn_ppm_up_fwd(const void* feats, int dtype, int N, int H, int W, void* y, int ldy, int coff,
+                     void* stream);
+int fscnn_ppm_up_bwd(const void* dy, int dtype, int N, int H, int W, int ldy, int coff,
+                     void* dfeats, void* stream);
+/* Dropout of an NHWC tensor x [N][H][W] x C (ldx): y = keep ? v / (1 - p) : 0, the keep mask a
+ * hash of (seed + seed_add, NCHW index); the seed by value, or read from the device slot
+ * seed_slot when not null.  x_scale / x_shift (optional, together): x is a raw conv output and
+ * v = relu(x*x_scale + x_shift) rounded to the storage type (bn_apply's output). */
+int fscnn_dropout(const void* x, int ldx, int dtype, int N, int H, int W, int C,
+                  unsigned long long seed, const unsigned long long* seed_slot,
+                  unsigned long long seed_add, float p, const float* x_scale,
+                  const float* x_shift, void* y, int ldy, void* stream);
+/* Train forms of the depthwise 3x3 conv (pad 1, stride 1 or 2, x NHWC [N][H][W][C]).
+ * fscnn_dw3x3_parts: BN records of the forward (dgrad 0) or of the dgrad (dgrad 1); -1 on bad
+ * arguments.
+ * fwd_train: z = conv(v), v = x or relu(x*in_scale + in_shift) (in_scale / in_shift together or
+ * null; padding stays zero), plus the batch statistics of the stored z finished to mean / invstd /
+ * scale / shift and the running statistics (nbt nullable).  part: parts*3*C floats.
+ * dgrad_bn: dx = the conv's input gradient, plus the BN backward sums of the stored dx for the
+ * BatchNorm whose output v was (its input z [N][H][W][C]; relu_mode 0 or 2 as in fscnn_bn_bwd)
+ * finished to dgamma / dbeta / coef [2][C].  part: parts*2*C floats; w 16-byte aligned.
+ * Both: counters 512 zeroed uint32 (left zero), tsum 32*3*1024 doubles; *in_kernel (nullable): 1
+ * when the kernel's last workgroups ran the finish, 0 when it was a launch of its own. */
+int fscnn_dw3x3_parts(int N, int H, int W, int C, int stride, int dtype, int dgrad);
+int fscnn_dw3x3_fwd_train(const void* x, int dtype, int N, int H, int W, int C, int stride,
+                          const float* w, const float* in_scale, const float* in_shift, void* z,
+                          float* part, unsigned* counters, double* tsum, const float* gamma,
+                          const float* beta, float* rmean, float* rvar, long long* nbt,
+                          float momentum, float* mean, float* invstd, float* scale, float* shift,
+                          int* in_kernel, void* stream);
+int fscnn_dw3x3_dgrad_bn(const void* dy, int dtype, int N, int H, int W, int C, int stride,
+                         const float* w, void* dx, const void* z, const float* mean,
+                         const float* invstd, const float* scale, const float* shift,
+                         int relu_mode, float* part, unsigned* counters, double* tsum,
+                         float* dgamma, float* dbeta, float* coef, int* in_kernel, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

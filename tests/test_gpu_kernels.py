@@ -1,7 +1,8 @@
 """Per-kernel parity of the HIP library (through the C ABI) against plain PyTorch fp32 CPU ops.
 
 fp32 tolerances are relative to the magnitude of the reference (exact-f32 MFMA / FMA paths differ
-from oneDNN only by summation order); bf16 tolerances reflect 8-bit mantissa storage.
+from oneDNN only by summation order); bf16 tolerances reflect 8-bit mantissa storage, fp16
+tolerances are the bf16 ones scaled by 2^-3 (11-bit mantissa).
 """
 import math
 
@@ -36,7 +37,15 @@ def nchw(t):
     return t.permute(0, 3, 1, 2).contiguous()
 
 
-TOL = {torch.float32: 2e-5, torch.bfloat16: 2e-2}
+TOL = {torch.float32: 2e-5, torch.bfloat16: 2e-2, torch.float16: 2.5e-3}
+
+
+def tol16(dt, f32, bf16):
+    """An inline tolerance: the fp32 figure, the bf16 figure, or for fp16 the bf16 figure scaled by
+    the mantissa (2^-3: 11 against 8 significant bits)."""
+    return {torch.float32: f32, torch.bfloat16: bf16, torch.float16: bf16 / 8}[dt]
+
+
 S = _lib.stream_ptr
 
 
@@ -44,7 +53,7 @@ def sync():
     torch.cuda.synchronize()
 
 
-@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("shape", [(2, 67, 131), (1, 128, 256), (3, 33, 300)])
 def test_conv0_fwd(dt, shape):
     N, H, W = shape
@@ -63,7 +72,7 @@ def test_conv0_fwd(dt, shape):
     close(nchw(y), ref, TOL[dt])
 
 
-@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("shape", [(2, 67, 131), (1, 128, 256), (3, 33, 1100), (2, 9, 8)])
 def test_conv0_wgrad(dt, shape):
     """MFMA wgrad of the first conv (K = pixels, tiles of 256, tails and multi-segment rows)."""
@@ -84,7 +93,7 @@ def test_conv0_wgrad(dt, shape):
     close(dw, wq.grad, 1e-5)
 
 
-@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("N,H,W,C,s", [(2, 17, 23, 32, 1), (2, 17, 23, 48, 2), (1, 64, 128, 384, 2),
                                        (2, 32, 64, 576, 1), (1, 31, 63, 768, 1), (2, 16, 32, 128, 1)])
 def test_dw3x3_fwd_bwd(dt, N, H, W, C, s):
@@ -118,10 +127,10 @@ def test_dw3x3_fwd_bwd(dt, N, H, W, C, s):
               _lib.ptr(slab), _lib.ptr(dw), S())
     sync()
     close(nchw(dx), xq.grad, TOL[dt])
-    close(dw, wq.grad, 1e-4 if dt == torch.float32 else 2e-2)
+    close(dw, wq.grad, tol16(dt, 1e-4, 2e-2))
 
 
-@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("M,N,K", [(1000, 48, 32), (4096, 384, 64), (777, 64, 384), (300, 96, 576),
                                    (513, 128, 768), (129, 19, 128), (40, 32, 128), (2048, 128, 256),
                                    (999, 2, 128), (3000, 128, 48), (5000, 576, 96), (2500, 768, 128),
@@ -166,10 +175,10 @@ def test_pw_gemm(dt, M, N, K):
     _lib.call("fscnn_pw_wgrad", M, N, K, _lib.ptr(Gd), ldg, _lib.ptr(Ad), K, _lib.ptr(slab),
               _lib.ptr(dW), _lib.dtype_code(dt), S())
     sync()
-    close(dW, ref3, 1e-4 if dt == torch.float32 else 1e-2)
+    close(dW, ref3, tol16(dt, 1e-4, 1e-2))
 
 
-@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("M,N,K", [(4099, 128, 128), (300, 128, 64)])
 def test_pw_gemm_residual_in_place(dt, M, N, K):
     # FFM eval form (models/fast_scnn.py:217-218): C = relu(A.W^T * sc + sh + C), C read and
@@ -190,7 +199,7 @@ def test_pw_gemm_residual_in_place(dt, M, N, K):
     close(C, ref, TOL[dt] * (10 if dt == torch.float32 else 1))
 
 
-@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("M,N,K", [(3001, 96, 64), (20001, 48, 32), (70000, 64, 64),
                                    (16384, 128, 768), (16385, 96, 384)])
 def test_gemm_bn_statistics(dt, M, N, K):
@@ -218,7 +227,7 @@ def test_gemm_bn_statistics(dt, M, N, K):
               _lib.ptr(beta), _lib.ptr(rm), _lib.ptr(rv), _lib.ptr(nbt), _lib.c_float(0.1),
               _lib.ptr(mean), _lib.ptr(invstd), _lib.ptr(scale), _lib.ptr(shift), S())
     sync()
-    tol = 1e-5 if dt == torch.float32 else 2e-3
+    tol = tol16(dt, 1e-5, 2e-3)
     close(mean, z.mean(0), tol)
     close(invstd, 1 / torch.sqrt(z.var(0, unbiased=False) + 1e-5), tol * 10)
     close(rm, 0.1 * z.mean(0), tol)
@@ -226,7 +235,7 @@ def test_gemm_bn_statistics(dt, M, N, K):
     assert int(nbt.item()) == 1
 
 
-@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("Hi,Wi,Ho,Wo,C", [(4, 8, 32, 64, 32), (1, 1, 15, 20, 32),
                                            (32, 64, 128, 256, 128), (16, 32, 128, 256, 24),
                                            (15, 20, 60, 80, 8), (6, 6, 32, 64, 32),
@@ -267,7 +276,7 @@ def test_bilinear_ac(dt, Hi, Wi, Ho, Wo, C):
     close(nchw(dx), xq.grad, TOL[dt] * 5)
 
 
-@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("H,W", [(32, 64), (15, 20), (4, 8), (24, 24), (2, 3)])
 def test_pyramid_pool(dt, H, W):
     N, C = 2, 128
@@ -296,7 +305,7 @@ def test_pyramid_pool(dt, H, W):
     close(nchw(dx), xq.grad, TOL[dt] * 5)
 
 
-@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16, torch.float16])
 def test_cross_entropy(dt):
     from fast_scnn_pytorch_amd.loss import cross_entropy
     N, C, H, W = 2, 19, 33, 65
@@ -311,7 +320,7 @@ def test_cross_entropy(dt):
     loss.backward()
     sync()
     assert abs(loss.item() - ref.item()) < 1e-5 * max(1.0, abs(ref.item()))
-    close(xd.grad, xq.grad, 1e-5 if dt == torch.float32 else 1e-2)
+    close(xd.grad, xq.grad, tol16(dt, 1e-5, 1e-2))
 
 
 def test_sgd():
