@@ -21,6 +21,17 @@ P_float = ctypes.POINTER(c_float)
 P_double = ctypes.POINTER(c_double)
 c_uint, P_ubyte = ctypes.c_uint, ctypes.POINTER(ctypes.c_ubyte)
 
+
+class AuxHead(ctypes.Structure):
+    """``fscnn_aux_head`` of include/fastscnn.h (the aux loss heads' criterion)."""
+    _fields_ = [("head", c_int), ("aux_weight", c_float), ("ignore_index", c_ll),
+                ("smooth", c_float), ("dice_weight", c_float), ("focal_weight", c_float),
+                ("alpha", c_float), ("gamma", c_float), ("thresh", c_float), ("min_kept", c_ll),
+                ("class_weight", c_vp)]
+
+
+P_aux_head = ctypes.POINTER(AuxHead)
+
 # name -> (restype, argtypes)
 SIGNATURES = {
     "fscnn_version": (c_char_p, []),
@@ -108,6 +119,13 @@ SIGNATURES = {
     "fscnn_forward_loss_ohem": (c_int, [c_vp, c_vp, c_int, c_vp, c_ll, c_float, c_ll, c_vp, c_vp,
                                         c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_ull,
                                         c_float, c_float, c_vp]),
+    "fscnn_aux_head_ws_bytes": (c_ll, [c_vp, c_int]),
+    "fscnn_aux_head_ws_offset": (c_ll, [c_vp, c_int, c_char_p, c_int]),
+    "fscnn_forward_loss_aux": (c_int, [c_vp, c_vp, c_int, c_vp, P_aux_head, c_vp, c_vp, c_vp, c_vp,
+                                       c_vp, c_vp, c_ull, c_float, c_float, c_vp]),
+    "fscnn_backward_loss_aux": (c_int, [c_vp, c_vp, P_aux_head, c_vp, c_int, c_vp, c_int, c_vp,
+                                        c_vp, c_vp, c_vp, c_vp, c_ull, c_float, c_int, c_int,
+                                        c_vp]),
     "fscnn_backward_dx": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_int, c_vp,
                                   c_vp, c_vp, c_vp, c_ull, c_float, c_int, c_int, c_vp]),
     "fscnn_prof_begin": (c_int, [c_int, c_int]),

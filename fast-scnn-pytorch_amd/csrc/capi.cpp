@@ -972,6 +972,110 @@ int fscnn_forward_loss_ohem(const fscnn_plan* plan, const void* x, int x_dtype,
   GUARD(net_forward(plan->plan, r));
 }
 
+long long fscnn_aux_head_ws_bytes(const fscnn_plan* plan, int head) {
+  if (!plan) {
+    set_error("fscnn_aux_head_ws_bytes: null plan");
+    return E_INVALID;
+  }
+  AuxHeadWs l;
+  if (!aux_head_ws(plan->plan, head, l)) return E_INVALID;
+  return (long long)l.bytes;
+}
+
+long long fscnn_aux_head_ws_offset(const fscnn_plan* plan, int head, const char* field, int which) {
+  if (!plan || !field || which < 0 || which > 1) {
+    set_error("fscnn_aux_head_ws_offset: null argument / which=%d", which);
+    return E_INVALID;
+  }
+  AuxHeadWs l;
+  if (!aux_head_ws(plan->plan, head, l)) return E_INVALID;
+  const std::string f = field;
+  const bool ohem = head == HEAD_OHEM, dice = head == HEAD_DICE;
+  if (f == "pair") return (long long)l.pair[which];
+  if (f == "stats" && dice) return (long long)l.stats[which];
+  if (f == "prob" && ohem) return (long long)l.prob[which];
+  if (f == "thr" && ohem) return (long long)l.thr[which];
+  if (f == "counts" && ohem) return (long long)l.counts[which];
+  set_error("fscnn_aux_head_ws_offset: head %d has no field '%s'", head, field);
+  return E_INVALID;
+}
+
+// the checks both aux loss entries share (after the null checks, before anything is launched),
+// and the head's fields of RunArgs
+static int aux_head_args(const char* who, const fscnn_plan* plan, const fscnn_aux_head* h,
+                         RunArgs& r) {
+  AuxHeadWs l;
+  if (!aux_head_ws(plan->plan, h->head, l)) {
+    const std::string why = fscnn_last_error();
+    set_error("%s: %s", who, why.c_str());
+    return E_INVALID;
+  }
+  if (h->head == HEAD_OHEM && h->min_kept < 0) {
+    set_error("%s: min_kept=%lld", who, h->min_kept);
+    return E_INVALID;
+  }
+  const int C = plan->plan.net->num_classes;
+  if (!ohem_head_ok(C) || (h->head == HEAD_DICE && C < 2)) {
+    set_error("%s: %d classes (the fused heads take 1 .. 32, the Dice head from 2)", who, C);
+    return E_UNSUPPORTED;
+  }
+  if (h->head == HEAD_DICE && h->focal_weight != 0.f) {
+    set_error("%s: focal_weight=%g (the aux Dice head is plain Dice: the reference has no "
+              "two-output Focal+Dice criterion)", who, h->focal_weight);
+    return E_UNSUPPORTED;
+  }
+  r.aux_loss = 1; r.head = h->head; r.aux_weight = h->aux_weight;
+  r.ignore_index = h->head == HEAD_DICE ? -1 : h->ignore_index;
+  if (h->head == HEAD_DICE) {
+    r.smooth = h->smooth; r.dice_weight = h->dice_weight; r.focal_weight = h->focal_weight;
+    r.alpha = h->alpha; r.gamma = h->gamma;
+  }
+  if (h->head == HEAD_OHEM) {
+    r.ohem_thresh = h->thresh; r.ohem_min_kept = h->min_kept; r.ohem_weight = h->class_weight;
+  }
+  return OK;
+}
+
+int fscnn_forward_loss_aux(const fscnn_plan* plan, const void* x, int x_dtype,
+                           const long long* target, const fscnn_aux_head* h, float* loss_out,
+                           const float* params, float* running, long long* nbt, void* ws,
+                           void* head_ws, unsigned long long seed, float dropout_p, float momentum,
+                           void* stream) {
+  if (!plan || !x || !target || !h || !loss_out || !params || !running || !ws || !head_ws) {
+    set_error("fscnn_forward_loss_aux: null argument");
+    return E_INVALID;
+  }
+  RunArgs r{};
+  if (int rc = aux_head_args("fscnn_forward_loss_aux", plan, h, r)) return rc;
+  r.x = x; r.x_dtype = x_dtype; r.out = nullptr; r.out_dtype = plan->plan.dtype;
+  r.P = params; r.R = running; r.NBT = nbt; r.ws = ws;
+  r.seed = seed; r.dropout_p = dropout_p; r.momentum = momentum; r.st = S(stream);
+  r.target = target; r.loss3 = loss_out; r.head_ws = head_ws;
+  GUARD(net_forward(plan->plan, r));
+}
+
+int fscnn_backward_loss_aux(const fscnn_plan* plan, const float* grad_loss,
+                            const fscnn_aux_head* h, const void* x, int x_dtype, void* dx,
+                            int dx_dtype, const float* params, float* grads, void* ws, void* bws,
+                            void* head_ws, unsigned long long seed, float dropout_p,
+                            int stage_from, int stage_to, void* stream) {
+  if (!plan || !grad_loss || !h || !x || !params || !grads || !ws || !bws || !head_ws) {
+    set_error("fscnn_backward_loss_aux: null argument");
+    return E_INVALID;
+  }
+  RunArgs r{};
+  if (int rc = aux_head_args("fscnn_backward_loss_aux", plan, h, r)) return rc;
+  if (dx && h->head == HEAD_DICE) {
+    set_error("fscnn_backward_loss_aux: the Dice head does not form the input gradient");
+    return E_INVALID;
+  }
+  r.gloss = grad_loss; r.head_ws = head_ws;
+  r.x = x; r.x_dtype = x_dtype; r.dx = dx; r.dx_dtype = dx_dtype;
+  r.P = params; r.G = grads; r.ws = ws; r.bws = bws;
+  r.seed = seed; r.dropout_p = dropout_p; r.st = S(stream);
+  GUARD(net_backward(plan->plan, r, stage_from, stage_to));
+}
+
 int fscnn_backward_dx(const fscnn_plan* plan, const void* dout, const void* daux,
                       const float* grad_loss, const float* loss2, const void* x, int x_dtype,
                       void* dx, int dx_dtype, const float* params, float* grads, void* ws,

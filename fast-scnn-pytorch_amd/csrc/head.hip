@@ -741,25 +741,42 @@ int ce_head(const CeHeadArgs& a, float* out2, int dtype, hipStream_t st) {
 template <typename T>
 __global__ __launch_bounds__(256) void ce_head_scale_kernel(const float* g_raw, T* g, int M, int C,
                                                             int ld, const float* gout,
-                                                            const float* out2) {
+                                                            const float* out2, float weight) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= M * ld) return;
   const int c = i % ld;
-  const float s = gout[0] / out2[1];
+  const float s = gout[0] * weight / out2[1];  // (weight 1: the single-output head, bit for bit)
   // own-row plane + the spill of the row above (fixed order)
   st1(g + i, c < C ? (g_raw[i] + g_raw[(size_t)M * ld + i]) * s : 0.f);
 }
 
 int ce_head_scale(const float* g_raw, void* g, long long M, int C, int ld, const float* gout,
-                  const float* out2, int dtype, hipStream_t st) {
+                  const float* out2, int dtype, hipStream_t st, float weight) {
   const int total = (int)(M * ld);
   if (dtype == DT_F32)
-    prof_launch(ce_head_scale_kernel<float>, cdiv(total, 256), 256, 0, st, g_raw, (float*)g, (int)M, C, ld, gout, out2);
+    prof_launch(ce_head_scale_kernel<float>, cdiv(total, 256), 256, 0, st, g_raw, (float*)g, (int)M, C, ld, gout, out2, weight);
   else if (dtype == DT_F16)
-    prof_launch(ce_head_scale_kernel<f16>, cdiv(total, 256), 256, 0, st, g_raw, (f16*)g, (int)M, C, ld, gout, out2);
+    prof_launch(ce_head_scale_kernel<f16>, cdiv(total, 256), 256, 0, st, g_raw, (f16*)g, (int)M, C, ld, gout, out2, weight);
   else
-    prof_launch(ce_head_scale_kernel<bf16>, cdiv(total, 256), 256, 0, st, g_raw, (bf16*)g, (int)M, C, ld, gout, out2);
+    prof_launch(ce_head_scale_kernel<bf16>, cdiv(total, 256), 256, 0, st, g_raw, (bf16*)g, (int)M, C, ld, gout, out2, weight);
   return check_launch("ce_head_scale");
+}
+
+// the criterion over (out, aux_out): main + aux_weight * aux, and the two unweighted terms
+__global__ void aux_loss_combine_kernel(const float* main, const float* aux, float aux_weight,
+                                        float* out3) {
+  if (threadIdx.x == 0) {
+    const float m = main[0], a = aux[0];
+    out3[0] = fmaf(aux_weight, a, m);
+    out3[1] = m;
+    out3[2] = a;
+  }
+}
+
+int aux_loss_combine(const float* main, const float* aux, float aux_weight, float* out3,
+                     hipStream_t st) {
+  prof_launch(aux_loss_combine_kernel, 1, 64, 0, st, main, aux, aux_weight, out3);
+  return check_launch("aux_loss_combine");
 }
 
 // ---- Dice / Focal+Dice head (utils/loss.py:12-100) -------------------------------------------
@@ -1125,15 +1142,19 @@ int dice_head(const DiceHeadArgs& a0, void* head_ws, float* loss, double* stats,
 }
 
 // g[m][c] = gout * (a Ga + b Gb + f Gf) (two classes: channel 1, channel 0 its negative) or
-// gout * the combined plane (general C); own-row plane + the spill of the row above, fixed order
+// gout * the combined plane (general C); own-row plane + the spill of the row above, fixed order;
+// gout is taken times `weight` (1: the single-output head, bit for bit; the aux head: aux_weight
+// -- the general-C plane already holds a, b, f, so the factor cannot ride in wd / wf)
 template <typename T>
 __global__ __launch_bounds__(256) void dice_head_scale_kernel(const float* planes, T* g, int M,
                                                               int C, int ld, const float* gout,
                                                               const double* stats, float smooth,
-                                                              float wd, float wf, double npix) {
+                                                              float wd, float wf, double npix,
+                                                              float weight) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= M * ld) return;
   const int c = i % ld, m = i / ld;
+  const float go = gout[0] * weight;
   float v = 0.f;
   if (C == 2) {
     if (c < 2) {
@@ -1141,25 +1162,25 @@ __global__ __launch_bounds__(256) void dice_head_scale_kernel(const float* plane
       const float* o = planes + (size_t)m * 3;
       const float* s = planes + ((size_t)M + m) * 3;
       v = k.a * (o[0] + s[0]) + k.b * (o[1] + s[1]) + k.f * (o[2] + s[2]);
-      v = (c == 1 ? v : -v) * gout[0];
+      v = (c == 1 ? v : -v) * go;
     }
   } else if (c < C) {
-    v = (planes[i] + planes[(size_t)M * ld + i]) * gout[0];
+    v = (planes[i] + planes[(size_t)M * ld + i]) * go;
   }
   st1(g + i, v);
 }
 
 int dice_head_scale(const void* head_ws, void* g, long long M, int C, int ld, const float* gout,
                     const double* stats, float smooth, float wd, float wf, double npix, int dtype,
-                    hipStream_t st) {
+                    hipStream_t st, float weight) {
   const int total = (int)(M * ld);
   const float* pl = (const float*)head_ws;
   if (dtype == DT_F32)
-    prof_launch(dice_head_scale_kernel<float>, cdiv(total, 256), 256, 0, st, pl, (float*)g, (int)M, C, ld, gout, stats, smooth, wd, wf, npix);
+    prof_launch(dice_head_scale_kernel<float>, cdiv(total, 256), 256, 0, st, pl, (float*)g, (int)M, C, ld, gout, stats, smooth, wd, wf, npix, weight);
   else if (dtype == DT_F16)
-    prof_launch(dice_head_scale_kernel<f16>, cdiv(total, 256), 256, 0, st, pl, (f16*)g, (int)M, C, ld, gout, stats, smooth, wd, wf, npix);
+    prof_launch(dice_head_scale_kernel<f16>, cdiv(total, 256), 256, 0, st, pl, (f16*)g, (int)M, C, ld, gout, stats, smooth, wd, wf, npix, weight);
   else
-    prof_launch(dice_head_scale_kernel<bf16>, cdiv(total, 256), 256, 0, st, pl, (bf16*)g, (int)M, C, ld, gout, stats, smooth, wd, wf, npix);
+    prof_launch(dice_head_scale_kernel<bf16>, cdiv(total, 256), 256, 0, st, pl, (bf16*)g, (int)M, C, ld, gout, stats, smooth, wd, wf, npix, weight);
   return check_launch("dice_head_scale");
 }
 

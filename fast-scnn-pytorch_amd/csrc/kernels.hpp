@@ -711,18 +711,22 @@ bool ce_head_reads_tgt8(int C, int ldl, int W, int dtype);
 // targets [n] int64 -> int8: t if 0 <= t < C and t != ignore_index, else -1 (C <= 127)
 int ce_pack_targets(const long long* t, long long n, int C, long long ignore_index,
                     signed char* out, hipStream_t st);
-// g[m][c] = g_raw[m][c] * gout / count  (c < C; pad columns zeroed)
+// g[m][c] = g_raw[m][c] * (gout * weight) / count  (c < C; pad columns zeroed)
 int ce_head_scale(const float* g_raw, void* g, long long M, int C, int ld, const float* gout,
-                  const float* out2, int dtype, hipStream_t st);
+                  const float* out2, int dtype, hipStream_t st, float weight = 1.f);
+// the two-output criterion (aux nets): out3 = (fmaf(aux_weight, aux, main), main, aux) from the
+// heads' own device outputs main[0] / aux[0]
+int aux_loss_combine(const float* main, const float* aux, float aux_weight, float* out3,
+                     hipStream_t st);
 // Dice / Focal+Dice head: loss[0] and stats[4] (I, S, T, F; fp64) are device outputs; head_ws
 // (dice_head_ws_bytes, 256-B aligned) keeps the coefficient planes for dice_head_scale, which
-// writes g = gout * (a Ga + b Gb + f Gf) (pad columns zeroed) in the plan dtype
+// writes g = gout * weight * (a Ga + b Gb + f Gf) (pad columns zeroed) in the plan dtype
 long long dice_head_ws_bytes(int N, int Hl, int Wl, int C, int ldl);
 int dice_head(const DiceHeadArgs& a, void* head_ws, float* loss, double* stats, int dtype,
               hipStream_t st);
 int dice_head_scale(const void* head_ws, void* g, long long M, int C, int ld, const float* gout,
                     const double* stats, float smooth, float wd, float wf, double npix, int dtype,
-                    hipStream_t st);
+                    hipStream_t st, float weight = 1.f);
 // OHEM head: loss2 = (weighted mean loss over the kept pixels, sum of kept weights) and g_raw in
 // the CE head's format (ce_head_scale finishes it); prob / thr / counts / work as for ohem_prob /
 // ohem_threshold_dev, the counters zeroed by the call.  ohem_head_ok: 1 .. 32 classes.

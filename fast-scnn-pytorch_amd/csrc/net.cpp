@@ -363,6 +363,7 @@ int plan_build(const Net& net, int N, int H, int W, int dtype, int train, Plan& 
   nm("f", pl.f, M2, 128, 128, 0);
   nm("drop", pl.drop, M2, 128, 128, 0);
   nm("logits", pl.logits, M2, net.num_classes, pl.Cp, 0);
+  if (net.aux) nm("aux_logits", pl.aux_logits, M2, net.num_classes, pl.Cp, 0);
 
   if (train) {
     const int C = net.num_classes;
@@ -1280,34 +1281,22 @@ struct Exec {
         set_error("forward_loss needs a training plan (train=1)");
         return E_INVALID;
       }
-      if (r.head == HEAD_DICE) {
-        g_prof_tag = "head (upsample + dice)";
-        DiceHeadArgs h{};
-        h.N = N; h.C = net.num_classes; h.Hl = pl.H3; h.Wl = pl.W3; h.H = pl.H; h.W = pl.W;
-        h.logits = W(pl.logits); h.ldl = pl.Cp; h.target = r.target;
-        if (pack) h.tgt8 = (const signed char*)W(pl.tgt8);
-        h.alpha = r.alpha; h.gamma = r.gamma; h.focal = r.focal_weight != 0.f;
-        h.smooth = r.smooth; h.wd = r.dice_weight; h.wf = r.focal_weight;
-        return dice_head(h, r.head_ws, r.loss2, r.dice_stats, dt, r.st);
+      if (r.aux_loss) {
+        // both outputs of an aux net: the same head kernels once per set of low-res logits (one
+        // target pack serves both), then the criterion's sum
+        if (!aux_layout()) return E_INVALID;
+        TRY(forward_aux(false));
+        const HeadBufs hm = aux_head_bufs(0), ha = aux_head_bufs(1);
+        TRY(loss_head(hm, pack, false));
+        TRY(loss_head(ha, pack, true));
+        g_prof_tag = "head (main + aux_weight * aux)";
+        return aux_loss_combine(hm.out, ha.out, r.aux_weight, r.loss3, r.st);
       }
-      if (r.head == HEAD_OHEM) {
-        g_prof_tag = "head (upsample + OHEM cross entropy)";
-        OhemHeadArgs h{};
-        h.N = N; h.C = net.num_classes; h.Hl = pl.H3; h.Wl = pl.W3; h.H = pl.H; h.W = pl.W;
-        h.logits = W(pl.logits); h.ldl = pl.Cp; h.target = r.target; h.ignore_index = r.ignore_index;
-        if (pack) h.tgt8 = (const signed char*)W(pl.tgt8);
-        h.weight = r.ohem_weight; h.thresh = r.ohem_thresh; h.prob = r.ohem_prob;
-        h.thr = r.ohem_thr; h.counts = r.ohem_counts;
-        h.g_raw = Wf(pl.g_raw); h.part = Wf(pl.head_part);
-        return ohem_head(h, r.ohem_min_kept, r.ohem_work, r.loss2, dt, r.st);
-      }
-      g_prof_tag = "head (upsample + cross entropy)";
-      CeHeadArgs h{};
-      h.N = N; h.C = net.num_classes; h.Hl = pl.H3; h.Wl = pl.W3; h.H = pl.H; h.W = pl.W;
-      h.logits = W(pl.logits); h.ldl = pl.Cp; h.target = r.target; h.ignore_index = r.ignore_index;
-      h.g_raw = Wf(pl.g_raw); h.part = Wf(pl.head_part);
-      if (pack) h.tgt8 = (const signed char*)W(pl.tgt8);
-      return ce_head(h, r.loss2, dt, r.st);
+      HeadBufs b;
+      b.logits = W(pl.logits); b.g_raw = Wf(pl.g_raw); b.part = Wf(pl.head_part);
+      b.out = r.loss2; b.dice_ws = r.head_ws; b.dice_stats = r.dice_stats;
+      b.prob = r.ohem_prob; b.thr = r.ohem_thr; b.counts = r.ohem_counts; b.work = r.ohem_work;
+      return loss_head(b, pack, false);
     }
     // ---- final bilinear (align_corners) to NCHW ----
     g_prof_tag = "head (upsample)";
@@ -1340,6 +1329,77 @@ struct Exec {
     }
     const int dtc = dt;
     return side_launch([g, dtc](hipStream_t s) { return gemm_nt(g, dtc, s); });
+  }
+
+  // the buffers of one run of the fused training head (r.head) over one set of low-res logits
+  struct HeadBufs {
+    const void* logits = nullptr;
+    float* g_raw = nullptr;      // CE / OHEM: the two gradient planes
+    float* part = nullptr;       // CE / OHEM: the loss partials
+    float* out = nullptr;        // (mean, count); Dice: the loss scalar
+    void* dice_ws = nullptr;     // Dice: coefficient planes + partials (dice_head_ws_bytes)
+    double* dice_stats = nullptr;
+    float* prob = nullptr;       // OHEM
+    float* thr = nullptr;
+    unsigned long long* counts = nullptr;
+    unsigned* work = nullptr;
+  };
+  int loss_head(const HeadBufs& b, bool pack, bool aux_out) {
+    const int N = pl.N;
+    if (r.head == HEAD_DICE) {
+      g_prof_tag = aux_out ? "auxlayer head (upsample + dice)" : "head (upsample + dice)";
+      DiceHeadArgs h{};
+      h.N = N; h.C = net.num_classes; h.Hl = pl.H3; h.Wl = pl.W3; h.H = pl.H; h.W = pl.W;
+      h.logits = b.logits; h.ldl = pl.Cp; h.target = r.target;
+      if (pack) h.tgt8 = (const signed char*)W(pl.tgt8);
+      h.alpha = r.alpha; h.gamma = r.gamma; h.focal = r.focal_weight != 0.f;
+      h.smooth = r.smooth; h.wd = r.dice_weight; h.wf = r.focal_weight;
+      return dice_head(h, b.dice_ws, b.out, b.dice_stats, dt, r.st);
+    }
+    if (r.head == HEAD_OHEM) {
+      g_prof_tag = aux_out ? "auxlayer head (upsample + OHEM cross entropy)"
+                           : "head (upsample + OHEM cross entropy)";
+      OhemHeadArgs h{};
+      h.N = N; h.C = net.num_classes; h.Hl = pl.H3; h.Wl = pl.W3; h.H = pl.H; h.W = pl.W;
+      h.logits = b.logits; h.ldl = pl.Cp; h.target = r.target; h.ignore_index = r.ignore_index;
+      if (pack) h.tgt8 = (const signed char*)W(pl.tgt8);
+      h.weight = r.ohem_weight; h.thresh = r.ohem_thresh; h.prob = b.prob;
+      h.thr = b.thr; h.counts = b.counts;
+      h.g_raw = b.g_raw; h.part = b.part;
+      return ohem_head(h, r.ohem_min_kept, b.work, b.out, dt, r.st);
+    }
+    g_prof_tag = aux_out ? "auxlayer head (upsample + cross entropy)"
+                         : "head (upsample + cross entropy)";
+    CeHeadArgs h{};
+    h.N = N; h.C = net.num_classes; h.Hl = pl.H3; h.Wl = pl.W3; h.H = pl.H; h.W = pl.W;
+    h.logits = b.logits; h.ldl = pl.Cp; h.target = r.target; h.ignore_index = r.ignore_index;
+    h.g_raw = b.g_raw; h.part = b.part;
+    if (pack) h.tgt8 = (const signed char*)W(pl.tgt8);
+    return ce_head(h, b.out, dt, r.st);
+  }
+  // the aux loss heads' layout of r.head_ws, computed once per call (false: error set)
+  AuxHeadWs auxl;
+  int auxl_state = 0;  // 0 not computed, 1 valid, -1 refused
+  bool aux_layout() {
+    if (!auxl_state) auxl_state = aux_head_ws(pl, r.head, auxl) ? 1 : -1;
+    return auxl_state > 0;
+  }
+  // ... of the aux loss heads: head i (0 main, 1 aux) over r.head_ws (after aux_layout())
+  HeadBufs aux_head_bufs(int i) {
+    const AuxHeadWs& l = auxl;
+    char* hw = (char*)r.head_ws;
+    HeadBufs b;
+    b.logits = i ? W(pl.aux_logits) : W(pl.logits);
+    b.g_raw = i ? (float*)(hw + l.g_raw) : Wf(pl.g_raw);
+    b.part = i ? (float*)(hw + l.part) : Wf(pl.head_part);
+    b.out = (float*)(hw + l.pair[i]);
+    b.dice_ws = hw + l.dice[i];
+    b.dice_stats = (double*)(hw + l.stats[i]);
+    b.prob = (float*)(hw + l.prob[i]);
+    b.thr = (float*)(hw + l.thr[i]);
+    b.counts = (unsigned long long*)(hw + l.counts[i]);
+    b.work = (unsigned*)(hw + l.work);
+    return b;
   }
 
   // aux head (models/fast_scnn.py:24-31,42-45) on the LearningToDownsample output l2pw.a
@@ -1393,18 +1453,32 @@ struct Exec {
     g_prof_tag = "auxlayer (backward)";
     const int N = pl.N, C = net.num_classes;
     const Unit& u = pl.aux0;
-    AxisBwdArgs a{};
-    a.n_o1 = (long long)N * C * pl.H; a.n_o2 = 1; a.Lout = pl.W; a.Lin = pl.W3; a.n_in = 1;
-    a.g = r.daux; a.g_s1 = pl.W; a.g_s2 = 0; a.g_idx = 1; a.g_in = 0;
-    a.d = Bw(pl.t_up); a.d_s1 = pl.W3; a.d_s2 = 0; a.d_idx = 1; a.d_in = 0;
-    TRY(axis_bwd(a, dt, DT_F32, r.st));
-    AxisBwdArgs b{};
-    b.n_o1 = N; b.n_o2 = C; b.Lout = pl.H; b.Lin = pl.H3; b.n_in = pl.W3;
-    b.g = Bw(pl.t_up); b.g_s1 = (long long)C * pl.H * pl.W3; b.g_s2 = (long long)pl.H * pl.W3;
-    b.g_idx = pl.W3; b.g_in = 1;
-    b.d = Bw(pl.g_auxlog); b.d_s1 = (long long)pl.H3 * pl.W3 * pl.Cp; b.d_s2 = 1;
-    b.d_idx = (long long)pl.W3 * pl.Cp; b.d_in = pl.Cp;
-    TRY(axis_bwd(b, DT_F32, dt, r.st));
+    if (r.aux_loss) {
+      // aux loss head: its low-res gradient was gathered in the forward; scale it by
+      // aux_weight * dL/dloss (/ count) straight into g_auxlog -- no upsample backward
+      if (!aux_layout()) return E_INVALID;
+      const HeadBufs hb = aux_head_bufs(1);
+      if (r.head == HEAD_DICE)
+        TRY(dice_head_scale(hb.dice_ws, Bw(pl.g_auxlog), u.M, C, pl.Cp, r.gloss, hb.dice_stats,
+                            r.smooth, r.dice_weight, r.focal_weight, (double)N * pl.H * pl.W, dt,
+                            r.st, r.aux_weight));
+      else
+        TRY(ce_head_scale(hb.g_raw, Bw(pl.g_auxlog), u.M, C, pl.Cp, r.gloss, hb.out, dt, r.st,
+                          r.aux_weight));
+    } else {
+      AxisBwdArgs a{};
+      a.n_o1 = (long long)N * C * pl.H; a.n_o2 = 1; a.Lout = pl.W; a.Lin = pl.W3; a.n_in = 1;
+      a.g = r.daux; a.g_s1 = pl.W; a.g_s2 = 0; a.g_idx = 1; a.g_in = 0;
+      a.d = Bw(pl.t_up); a.d_s1 = pl.W3; a.d_s2 = 0; a.d_idx = 1; a.d_in = 0;
+      TRY(axis_bwd(a, dt, DT_F32, r.st));
+      AxisBwdArgs b{};
+      b.n_o1 = N; b.n_o2 = C; b.Lout = pl.H; b.Lin = pl.H3; b.n_in = pl.W3;
+      b.g = Bw(pl.t_up); b.g_s1 = (long long)C * pl.H * pl.W3; b.g_s2 = (long long)pl.H * pl.W3;
+      b.g_idx = pl.W3; b.g_in = 1;
+      b.d = Bw(pl.g_auxlog); b.d_s1 = (long long)pl.H3 * pl.W3 * pl.Cp; b.d_s2 = 1;
+      b.d_idx = (long long)pl.W3 * pl.Cp; b.d_in = pl.Cp;
+      TRY(axis_bwd(b, DT_F32, dt, r.st));
+    }
     const bool drop = r.dropout_p > 0.f;
     TRY(pw_bwd(net.aux4, u.M, plain(Bw(pl.g_auxlog), pl.Cp), raw(drop ? W(pl.aux_drop) : W(u.a), 32),
                drop ? Bw(pl.g_aux) : Bw(u.ga), 32));
@@ -1665,14 +1739,21 @@ struct Exec {
   int backward_head() {
     g_prof_tag = "head (backward) + classifier.conv";
     const int N = pl.N, C = net.num_classes;
+    // the forward head's own outputs (aux loss heads: the main head's, in head_ws)
+    HeadBufs hb;
+    hb.g_raw = Wf(pl.g_raw); hb.out = r.loss2; hb.dice_ws = r.head_ws; hb.dice_stats = r.dice_stats;
+    if (r.aux_loss) {
+      if (!aux_layout()) return E_INVALID;
+      hb = aux_head_bufs(0);
+    }
     if (r.gloss && r.head == HEAD_DICE) {
       // fused Dice head: combine the forward's coefficient planes with the device-resident sums
-      TRY(dice_head_scale(r.head_ws, Bw(pl.g_logits), pl.c2pw.M, C, pl.Cp, r.gloss, r.dice_stats,
+      TRY(dice_head_scale(hb.dice_ws, Bw(pl.g_logits), pl.c2pw.M, C, pl.Cp, r.gloss, hb.dice_stats,
                           r.smooth, r.dice_weight, r.focal_weight, (double)N * pl.H * pl.W, dt,
                           r.st));
     } else if (r.gloss) {
       // fused head: the low-res logits gradient was gathered in the forward; scale by dL/dloss / count
-      TRY(ce_head_scale(Wf(pl.g_raw), Bw(pl.g_logits), pl.c2pw.M, C, pl.Cp, r.gloss, r.loss2, dt,
+      TRY(ce_head_scale(hb.g_raw, Bw(pl.g_logits), pl.c2pw.M, C, pl.Cp, r.gloss, hb.out, dt,
                         r.st));
     } else {
       // final upsample: W pass (NCHW rows) then H pass into NHWC low-res logits grad
@@ -1971,7 +2052,8 @@ std::vector<uint64_t> run_key(int kind, int s0, int s1, const RunArgs& r) {
           (uint64_t)r.head, fbits(r.smooth), fbits(r.dice_weight), fbits(r.focal_weight),
           fbits(r.alpha), fbits(r.gamma), P(r.head_ws), P(r.dice_stats), fbits(r.ohem_thresh),
           (uint64_t)r.ohem_min_kept, P(r.ohem_weight), P(r.ohem_prob), P(r.ohem_thr),
-          P(r.ohem_counts), P(r.ohem_work), (uint64_t)r.validate,
+          P(r.ohem_counts), P(r.ohem_work), (uint64_t)r.aux_loss, P(r.loss3),
+          (uint64_t)r.validate,
           fbits(r.aux_weight), P(r.counts), (uint64_t)r.e2e_ho, (uint64_t)r.e2e_wo,
           (uint64_t)r.e2e_softmax, (uint64_t)r.e2e_pdtype, (uint64_t)r.e2e_scale, P(r.e2e_probs),
           P(r.e2e_labels), (uint64_t)r.bev_hb, (uint64_t)r.bev_wb, (uint64_t)r.bev_min_width,
@@ -2059,6 +2141,47 @@ int run_graphed(const Plan& pl, std::vector<uint64_t> key, hipStream_t st, F&& b
 
 }  // namespace
 
+bool aux_head_ws(const Plan& pl, int head, AuxHeadWs& l) {
+  if (!pl.net->aux || pl.train != 1) {
+    set_error("fscnn_aux_head_ws_bytes: the aux loss heads need a training plan (train=1) of an "
+              "aux net");
+    return false;
+  }
+  if (head != HEAD_CE && head != HEAD_DICE && head != HEAD_OHEM) {
+    set_error("fscnn_aux_head_ws_bytes: head %d (0 CE, 1 Dice, 2 OHEM)", head);
+    return false;
+  }
+  size_t top = 0;
+  auto get = [&](size_t bytes) {
+    const size_t off = top;
+    top += (bytes + 255) / 256 * 256;
+    return off;
+  };
+  const size_t M2 = (size_t)pl.N * pl.H3 * pl.W3, npix = (size_t)pl.N * pl.H * pl.W;
+  l = AuxHeadWs();
+  for (int i = 0; i < 2; ++i) l.pair[i] = get(2 * 4);
+  if (head == HEAD_DICE) {
+    const size_t db = (size_t)dice_head_ws_bytes(pl.N, pl.H3, pl.W3, pl.net->num_classes, pl.Cp);
+    for (int i = 0; i < 2; ++i) {
+      l.stats[i] = get(4 * 8);
+      l.dice[i] = get(db);
+    }
+  } else {
+    l.g_raw = get(2 * M2 * pl.Cp * 4);
+    l.part = get((size_t)ce_head_parts(pl.N, pl.H3, pl.W3) * 2 * 4);
+  }
+  if (head == HEAD_OHEM) {
+    for (int i = 0; i < 2; ++i) {
+      l.prob[i] = get(npix * 4);
+      l.thr[i] = get(4);
+      l.counts[i] = get(2 * 8);
+    }
+    l.work = get(2056 * 4);
+  }
+  l.bytes = top;
+  return true;
+}
+
 int net_forward_impl(const Plan& pl, const RunArgs& r);
 int net_forward(const Plan& pl, const RunArgs& r) {
   const double t0 = g_host_prof ? host_now_us() : 0.0;
@@ -2071,11 +2194,17 @@ int net_forward_impl(const Plan& pl, const RunArgs& r) {
     set_error("fscnn_forward: input / output dtype codes must be 0 (fp32), 1 (bf16) or 2 (fp16)");
     return E_INVALID;
   }
-  if (pl.net->aux && r.target && !r.validate) {
-    set_error("forward_loss: the fused loss head covers the main output only (aux net)");
+  if (pl.net->aux && r.target && !r.validate && !r.aux_loss) {
+    set_error("forward_loss: the fused loss head covers the main output only (aux net; "
+              "fscnn_forward_loss_aux takes both outputs)");
     return E_UNSUPPORTED;
   }
-  if (pl.net->aux && !r.aux_out && !r.labels && !r.validate && r.e2e_ho <= 0) {
+  if (r.aux_loss && (!pl.net->aux || pl.train != 1 || !r.target || !r.loss3 || !r.head_ws)) {
+    set_error("fscnn_forward_loss_aux: needs a train = 1 plan of an aux net, target, loss_out "
+              "and head_ws");
+    return E_INVALID;
+  }
+  if (pl.net->aux && !r.aux_out && !r.labels && !r.validate && r.e2e_ho <= 0 && !r.aux_loss) {
     set_error("fscnn_forward: this net has the aux head; use fscnn_forward_aux");
     return E_INVALID;
   }
@@ -2109,7 +2238,12 @@ int net_backward_impl(const Plan& pl, const RunArgs& r, int stage_from, int stag
     set_error("net_backward: the plan was built for inference (train=0)");
     return E_INVALID;
   }
-  if (pl.net->aux && !r.daux) {
+  if (r.aux_loss && (!pl.net->aux || pl.train != 1 || !r.gloss || !r.head_ws)) {
+    set_error("fscnn_backward_loss_aux: needs a train = 1 plan of an aux net, grad_loss and "
+              "head_ws");
+    return E_INVALID;
+  }
+  if (pl.net->aux && !r.daux && !r.aux_loss) {
     set_error("fscnn_backward: this net has the aux head; use fscnn_backward_aux");
     return E_INVALID;
   }

@@ -205,6 +205,15 @@ struct RunArgs {
   float* ohem_thr = nullptr;
   unsigned long long* ohem_counts = nullptr;
   unsigned* ohem_work = nullptr;
+  // aux loss heads (aux nets, fscnn_forward_loss_aux): with aux_loss != 0 the forward runs the
+  // head `head` on the main and then on the aux low-res logits and writes loss3 = (main +
+  // aux_weight * aux, main, aux); the backward scales the main head's gradient as above and the
+  // aux head's, times aux_weight, straight into g_auxlog (no upsample backward).  The main head
+  // keeps the plan's g_raw / head_part; everything else both heads need lives in head_ws
+  // (aux_head_ws_bytes, AuxHeadWs), the (mean, count) pairs / Dice stats the backward reads
+  // included -- loss3 is only an output.
+  int aux_loss = 0;
+  float* loss3 = nullptr;
   // eval prediction: forward with labels != null writes argmax(upsampled logits) instead of out
   void* labels = nullptr;
   int label_u8 = 0;
@@ -240,6 +249,18 @@ struct RunArgs {
   void* dx = nullptr;
   int dx_dtype = 0;
 };
+
+// Layout of the aux loss heads' caller buffer (byte offsets, 256-B aligned; index 0 = main head,
+// 1 = aux head).  pair: the head's (mean, count) output, Dice: its loss scalar.  g_raw / part:
+// the aux head's CE / OHEM gradient planes and partials (the main head uses the plan's).  dice /
+// stats: each Dice head's coefficient planes (dice_head_ws_bytes) and double[4] sums.  prob / thr /
+// counts: each OHEM head's probability plane, threshold and counter pair; work: the select scratch.
+struct AuxHeadWs {
+  size_t pair[2] = {}, g_raw = 0, part = 0, dice[2] = {}, stats[2] = {}, prob[2] = {}, thr[2] = {},
+         counts[2] = {}, work = 0, bytes = 0;
+};
+// false (fscnn_last_error set): not an aux train = 1 plan, or an unknown head
+bool aux_head_ws(const Plan& pl, int head, AuxHeadWs& l);
 
 int net_forward(const Plan& pl, const RunArgs& r);
 int net_backward(const Plan& pl, const RunArgs& r, int stage_from, int stage_to);

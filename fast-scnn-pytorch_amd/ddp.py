@@ -161,3 +161,10 @@ class DistributedFastSCNN(torch.nn.Module):
         label probability) runs over this rank's shard, as it does per replica under the
         reference's DistributedDataParallel."""
         return self.module.forward_loss_ohem(x, target, criterion)
+
+    def forward_loss_aux(self, x, target, criterion):
+        """Fused forward + two-output loss of the local shard of an ``aux=True`` model
+        (``FastSCNN.forward_loss_aux``); backward all-reduces gradients per stage, the aux
+        layer's with the head stage that contains them.  Dice sums and OHEM thresholds are per
+        rank, as in ``forward_loss`` / ``forward_loss_ohem``."""
+        return self.module.forward_loss_aux(x, target, criterion)

@@ -342,6 +342,75 @@ def _ohem_spec(criterion):
                            % (type(criterion).__name__, e))
 
 
+def _aux_head_spec(criterion):
+    """The fused aux loss heads (``forward_loss_aux``) a two-output criterion maps to, as a tuple
+    whose second entry is ``aux_weight``:
+
+    ``("ce", aux_weight, ignore_index)``, ``("dice", aux_weight, smooth)`` or
+    ``("ohem", aux_weight, ignore_label, thresh, min_kept, weight_or_None)``.
+
+    Duck-typed like ``_head_spec`` / ``_ohem_spec``: ``MixSoftmaxCrossEntropyLoss``,
+    ``MixDiceLoss`` and ``MixSoftmaxCrossEntropyOHEMLoss`` of this package or of utils/loss.py
+    (what train.py:183-191 builds with ``--aux``).  A criterion with ``aux`` false, the
+    single-output criteria (``DiceLoss``, ``FocalDiceLoss``, ``SoftmaxCrossEntropyOHEMLoss``) and
+    anything unknown raise ``RuntimeError``."""
+    names = [c.__name__ for c in type(criterion).__mro__]
+    unfused = "use the unfused path, criterion(model(x), target)"
+    try:
+        if "MixSoftmaxCrossEntropyOHEMLoss" in names:
+            spec = ("ohem", float(criterion.aux_weight)) + _ohem_spec(criterion)[1:]
+        elif "MixDiceLoss" in names:
+            spec = ("dice", float(criterion.aux_weight), float(criterion.dice_loss.smooth))
+        elif "MixSoftmaxCrossEntropyLoss" in names:
+            spec = ("ce", float(criterion.aux_weight), int(criterion.ignore_index))
+        else:
+            raise RuntimeError("forward_loss_aux: no fused aux loss heads for %s (they take "
+                               "MixSoftmaxCrossEntropyLoss, MixDiceLoss and "
+                               "MixSoftmaxCrossEntropyOHEMLoss); %s"
+                               % (type(criterion).__name__, unfused))
+        aux = bool(criterion.aux)
+    except AttributeError as e:
+        raise RuntimeError("forward_loss_aux: %s lacks the criterion's attributes (%s); %s"
+                           % (type(criterion).__name__, e, unfused))
+    if not aux:
+        raise RuntimeError("forward_loss_aux: the criterion has aux=False (it would drop the aux "
+                           "output); build it with aux=True, or %s" % unfused)
+    return spec
+
+
+class _FastSCNNAuxLossFunction(torch.autograd.Function):
+    """Fused train step heads of an aux model: loss = L(out) + aux_weight * L(aux_out), both at
+    low resolution.  ``spec``: an ``_aux_head_spec`` tuple (OHEM: its weights on the device).  The
+    heads' state travels to the backward in one buffer, ``head_ws``; the returned loss is a tensor
+    of its own, which the backward never reads (the caller may scale it in place)."""
+
+    @staticmethod
+    def forward(ctx, x, target, spec, model, ar, *params):
+        if spec[0] == "dice" and ctx.needs_input_grad[0]:
+            raise RuntimeError("forward_loss_aux: the fused Dice head does not form the input "
+                               "image's gradient; use criterion(model(x), target)")
+        loss3, ws, seed, dt, xc, head, head_ws = model._run_forward_loss_aux(x, target, spec, ar)
+        ctx.model, ctx.ar = model, ar
+        ctx.ws, ctx.seed, ctx.dt, ctx.aux = ws, seed, dt, (head, head_ws, spec)
+        ctx.x_dtype = x.dtype
+        ctx.save_for_backward(xc, *params)
+        model._last_loss_terms = loss3[1:]
+        out = torch.empty((), dtype=loss3.dtype, device=loss3.device)
+        return out.set_(loss3.untyped_storage(), loss3.storage_offset(), (), ())
+
+    @staticmethod
+    def backward(ctx, gloss):
+        x = ctx.saved_tensors[0]
+        g = gloss.to(torch.float32).reshape(1).contiguous()
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        grads = ctx.model._run_backward(None, x, ctx.ws, ctx.seed, ctx.dt, ctx.ar, gloss=g,
+                                        dx=dx, aux_head=ctx.aux)
+        ctx.ws = ctx.ar = ctx.aux = None
+        if dx is not None and dx.dtype != ctx.x_dtype:
+            dx = dx.to(ctx.x_dtype)
+        return (dx, None, None, None, None) + tuple(grads)
+
+
 class _FastSCNNLossFunction(torch.autograd.Function):
     """Fused train step head: loss = criterion(upsample(logits_lowres), target) at low
     resolution.  ``head`` is the CE head's ignore_index (an int), a Dice ``_head_spec`` tuple or
@@ -794,8 +863,8 @@ class FastSCNN(nn.Module):
     def _run_forward_loss(self, x, target, ignore_index, ar):
         if self.aux:
             raise RuntimeError("forward_loss: the fused loss head covers the main output only; "
-                               "with aux=True use MixSoftmaxCrossEntropyLoss(aux=True)"
-                               "(model(x), target)")
+                               "with aux=True use forward_loss_aux(x, target, criterion), or "
+                               "MixSoftmaxCrossEntropyLoss(aux=True)(model(x), target)")
         if not x.is_cuda or not target.is_cuda:
             raise RuntimeError("FastSCNN.forward_loss: the HIP path needs ROCm device tensors")
         nat = self.native()
@@ -835,7 +904,8 @@ class FastSCNN(nn.Module):
         """The forward of the fused Dice / Focal+Dice head (``spec``: a Dice ``_head_spec``)."""
         if self.aux:
             raise RuntimeError("forward_loss: the fused loss head covers the main output only; "
-                               "with aux=True use MixDiceLoss(aux=True)(model(x), target)")
+                               "with aux=True use forward_loss_aux(x, target, criterion), or "
+                               "MixDiceLoss(aux=True)(model(x), target)")
         if not x.is_cuda or not target.is_cuda:
             raise RuntimeError("FastSCNN.forward_loss: the HIP path needs ROCm device tensors")
         if not 2 <= self.num_classes <= 32:
@@ -937,8 +1007,8 @@ class FastSCNN(nn.Module):
         are on the device)."""
         if self.aux:
             raise RuntimeError("forward_loss_ohem: the fused loss head covers the main output "
-                               "only; with aux=True use MixSoftmaxCrossEntropyOHEMLoss(aux=True)"
-                               "(model(x), target)")
+                               "only; with aux=True use forward_loss_aux(x, target, criterion), "
+                               "or MixSoftmaxCrossEntropyOHEMLoss(aux=True)(model(x), target)")
         if not x.is_cuda or not target.is_cuda:
             raise RuntimeError("FastSCNN.forward_loss_ohem: the HIP path needs ROCm device tensors")
         nat = self.native()
@@ -1010,14 +1080,133 @@ class FastSCNN(nn.Module):
             raise RuntimeError("FastSCNN.forward_loss_ohem: the HIP path needs ROCm device tensors")
         if self.aux:
             raise RuntimeError("forward_loss_ohem: the fused loss head covers the main output "
-                               "only; with aux=True use MixSoftmaxCrossEntropyOHEMLoss(aux=True)"
-                               "(model(x), target)")
+                               "only; with aux=True use forward_loss_aux(x, target, criterion), "
+                               "or MixSoftmaxCrossEntropyOHEMLoss(aux=True)(model(x), target)")
         head = spec[:4] + (self._ohem_weight(spec[4], x.device),)
         ar = self._exec_arena(x.device)
         return _FastSCNNLossFunction.apply(x, target, head, self, ar, *ar["params"])
 
+    def _run_forward_loss_aux(self, x, target, spec, ar):
+        """The forward of the fused aux loss heads (``spec``: an ``_aux_head_spec`` tuple whose
+        OHEM weights are on the device).  Returns the device ``loss3`` = (total, main, aux), the
+        ``fscnn_aux_head`` struct and the ``head_ws`` buffer the backward takes again."""
+        kind, aux_weight = spec[0], spec[1]
+        if not self.aux:
+            raise RuntimeError("forward_loss_aux: this model has no aux head (aux=False); use "
+                               "forward_loss / forward_loss_ohem, or the unfused path, "
+                               "criterion(model(x), target)")
+        if not x.is_cuda or not target.is_cuda:
+            raise RuntimeError("FastSCNN.forward_loss_aux: the HIP path needs ROCm device tensors")
+        if not (2 if kind == "dice" else 1) <= self.num_classes <= 32:
+            raise RuntimeError("forward_loss_aux: the fused heads take 1 .. 32 classes (Dice: "
+                               "2 .. 32); use the unfused path, criterion(model(x), target)")
+        nat = self.native()
+        N, _, H, W = x.shape
+        if tuple(target.shape) != (N, H, W):
+            raise RuntimeError("forward_loss_aux: target %s does not match input %s"
+                               % (tuple(target.shape), tuple(x.shape)))
+        if N < 2:
+            raise ValueError("Expected more than 1 value per channel when training, got input "
+                             "size torch.Size([1, 32, 1, 1])")
+        dt = self._compute_dtype(x, True)
+        x = self._input(x)
+        target = target.to(torch.int64).contiguous()
+        head = _lib.AuxHead()
+        head.aux_weight = aux_weight
+        head.ignore_index = -1
+        if kind == "ce":
+            head.head, head.ignore_index = 0, spec[2]
+        elif kind == "dice":  # MixDiceLoss: plain Dice on each output
+            head.head, head.smooth, head.dice_weight, head.focal_weight = 1, spec[2], 1.0, 0.0
+            head.alpha, head.gamma = 0.5, 2.0
+        else:
+            _, _, ign, thresh, min_kept, weight = spec
+            head.head, head.ignore_index, head.thresh, head.min_kept = 2, ign, thresh, min_kept
+            head.class_weight = weight.data_ptr() if weight is not None else None
+        from . import loss as _loss
+        if _loss.CHECK_TARGETS:
+            if kind == "dice":  # no ignore_index in Dice
+                bad = (target < 0) | (target >= self.num_classes)
+                if bool(bad.any()):
+                    raise IndexError("Target %d is out of bounds." % int(target[bad].flatten()[0]))
+            else:
+                _loss.check_targets(target, self.num_classes, int(head.ignore_index))
+        dev = x.device
+        plan, fw, _ = nat.plan(N, H, W, _lib.dtype_code(dt), True, dev)
+        hb = int(_lib.load().fscnn_aux_head_ws_bytes(plan, head.head))
+        if hb < 0:
+            _lib.check(hb, "fscnn_aux_head_ws_bytes")
+        ws = torch.empty(max(fw, 1), dtype=torch.uint8, device=dev)
+        head_ws = torch.empty(hb, dtype=torch.uint8, device=dev)
+        loss3 = torch.empty(3, dtype=torch.float32, device=dev)
+        p = self._dropout_p()
+        seed = 0
+        if p > 0:
+            fixed = getattr(self, "_dropout_seed", None)
+            seed = int(fixed) if fixed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
+        with torch.cuda.device(dev):
+            rc = _lib.load().fscnn_forward_loss_aux(
+                plan, _lib.ptr(x), _lib.dtype_code(x.dtype), _lib.ptr(target),
+                _lib.ctypes.byref(head), _lib.ptr(loss3), _lib.ptr(ar["P"]), _lib.ptr(ar["R"]),
+                _lib.ptr(ar["NBT"]), _lib.ptr(ws), _lib.ptr(head_ws), _lib.c_ull(seed),
+                _lib.c_float(p), _lib.c_float(self._momentum()), _lib.stream_ptr(dev))
+        if rc == E_UNSUPPORTED:  # nothing was launched
+            raise RuntimeError("forward_loss_aux: no fused aux loss heads for this model (%s); "
+                               "use the unfused path, criterion(model(x), target)"
+                               % _lib.load().fscnn_last_error().decode(errors="replace"))
+        _lib.check(rc, "fscnn_forward_loss_aux")
+        self._writeback(ar)
+        torch.autograd.graph.increment_version(ar["R"])
+        if getattr(self, "_keep_ws", False):
+            self._debug = {"plan": plan, "ws": ws, "dt": dt, "head_ws": head_ws}
+            if kind == "ohem":  # each head's plane, threshold and counters, as views of head_ws
+                def view(field, which, n, tdt):
+                    off = int(_lib.load().fscnn_aux_head_ws_offset(plan, 2, field, which))
+                    if off < 0:
+                        _lib.check(off, "fscnn_aux_head_ws_offset")
+                    nb = n * torch.tensor([], dtype=tdt).element_size()
+                    return head_ws[off:off + nb].view(tdt)
+                self._debug["ohem"] = [{"prob": view(b"prob", i, N * H * W, torch.float32)
+                                        .view(N, H, W),
+                                        "thr": view(b"thr", i, 1, torch.float32),
+                                        "counts": view(b"counts", i, 2, torch.int64),
+                                        # (weighted mean, sum of the kept pixels' weights)
+                                        "pair": view(b"pair", i, 2, torch.float32)}
+                                       for i in range(2)]
+        return loss3, ws, seed, dt, x, head, head_ws
+
+    def forward_loss_aux(self, x, target, criterion):
+        """Fused train-step heads of an ``aux=True`` model: ``criterion(self(x), target)`` =
+        ``L(out) + aux_weight * L(aux_out)`` of train.py:270-271 run with ``--aux``, both terms
+        computed from the low-res logits: no full-resolution logits or gradient of either output
+        is written and nothing is read back by the host.  Returns the scalar loss; requires train
+        mode, an aux model and a criterion built with ``aux=True``.
+
+        ``criterion`` (this package's or the reference's own object, ``_aux_head_spec``):
+        ``MixSoftmaxCrossEntropyLoss`` (CE head, the criterion's ``ignore_index``),
+        ``MixDiceLoss`` (Dice head; it does not form the input image's gradient) or
+        ``MixSoftmaxCrossEntropyOHEMLoss`` (OHEM head: each output has its own probability plane,
+        threshold and kept set, as utils/loss.py:191-198 calls the single-output law once per
+        prediction).  Anything else raises ``RuntimeError``: use ``criterion(model(x), target)``.
+
+        ``self._last_loss_terms`` is then the device fp32 tensor ``[L(out), L(aux_out)]``, the
+        unweighted terms (logging)."""
+        spec = _aux_head_spec(criterion)
+        if not self.training:
+            raise RuntimeError("forward_loss_aux is the training step; call model.train() first")
+        if not self.aux:
+            raise RuntimeError("forward_loss_aux: this model has no aux head (aux=False); use "
+                               "forward_loss / forward_loss_ohem, or the unfused path, "
+                               "criterion(model(x), target)")
+        if not x.is_cuda:
+            raise RuntimeError("FastSCNN.forward_loss_aux: the HIP path needs ROCm device tensors")
+        if spec[0] == "ohem":
+            spec = spec[:5] + (self._ohem_weight(spec[5], x.device),)
+        ar = self._exec_arena(x.device)
+        return _FastSCNNAuxLossFunction.apply(x, target, spec, self, ar, *ar["params"])
+
     def _run_backward(self, gout, x, ws, seed, dt, ar, gloss=None, loss2=None, gaux=None,
-                      mode=MODE_TRAIN, dx=None, dice=None):
+                      mode=MODE_TRAIN, dx=None, dice=None, aux_head=None):
         """The staged native backward of a MODE_TRAIN / MODE_EVAL_GRAD forward whose workspace
         is ``ws``; parameter gradients are views of one flat arena G, and ``dx`` (dense NCHW,
         the dtype of ``x``) receives the input gradient when given."""
@@ -1044,21 +1233,29 @@ class FastSCNN(nn.Module):
             # its end, so the main stream does not wait for the side stream between stages
             with torch.cuda.device(x.device):
                 self._backward_stage(plan, (0, 3), gout, gaux, gloss, loss2, x, ar, G, ws, bws,
-                                     seed, p, dx, dice)
+                                     seed, p, dx, dice, aux_head)
         else:
             for s in range(4):
                 with torch.cuda.device(x.device):
                     self._backward_stage(plan, (s, s), gout, gaux, gloss, loss2, x, ar, G, ws,
-                                         bws, seed, p, dx, dice)
+                                         bws, seed, p, dx, dice, aux_head)
                 b, e = nat.stage_ranges[s]
                 hook(s, G, b, e)
         return [G[off:off + numel].view(prm.shape)
                 for prm, (_, off, numel) in zip(ar["params"], nat.params)]
 
     def _backward_stage(self, plan, stages, gout, gaux, gloss, loss2, x, ar, G, ws, bws, seed, p,
-                        dx=None, dice=None):
+                        dx=None, dice=None, aux_head=None):
         s0, s1 = stages  # backward stages s0 .. s1 (0: head ... 3: LearningToDownsample)
-        if dice is not None:  # the fused Dice head: (spec, head_ws, stats) of its forward
+        if aux_head is not None:  # the fused aux loss heads: (struct, head_ws, spec) of the forward
+            head, head_ws, _ = aux_head
+            _lib.call("fscnn_backward_loss_aux", plan, _lib.ptr(gloss), _lib.ctypes.byref(head),
+                      _lib.ptr(x), _lib.dtype_code(x.dtype), _lib.ptr(dx),
+                      _lib.dtype_code(dx.dtype if dx is not None else x.dtype),
+                      _lib.ptr(ar["P"]), _lib.ptr(G), _lib.ptr(ws), _lib.ptr(bws),
+                      _lib.ptr(head_ws), _lib.c_ull(seed), _lib.c_float(p), s0, s1,
+                      _lib.stream_ptr(x.device))
+        elif dice is not None:  # the fused Dice head: (spec, head_ws, stats) of its forward
             (_, smooth, dw, fw, _, _), head_ws, stats = dice
             _lib.call("fscnn_backward_loss_dice", plan, _lib.ptr(gloss), _lib.ptr(stats),
                       _lib.c_float(smooth), _lib.c_float(dw), _lib.c_float(fw), _lib.ptr(x),

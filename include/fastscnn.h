@@ -453,6 +453,62 @@ int fscnn_forward_loss_ohem(const fscnn_plan* plan, const void* x, int x_dtype,
                             unsigned long long dropout_seed, float dropout_p, float momentum,
                             void* stream);
 
+/* The fused step heads for an aux net (FastSCNN(aux=True), what train.py builds with --aux):
+ * loss = L(out) + aux_weight * L(aux_out), the criteria of utils/loss.py:42-68 (MixDiceLoss),
+ * :103-124 (MixSoftmaxCrossEntropyLoss) and :179-206 (MixSoftmaxCrossEntropyOHEMLoss), where L is
+ * the single-output law of the heads above on each bilinearly upsampled output.  The head kernels
+ * run once on the main and once on the aux low-resolution logits (the aux head stops there: no
+ * full-resolution logits or gradient of either output exists); the OHEM head keeps a probability
+ * plane, threshold and kept set per output, as the reference calls its single-output law once per
+ * prediction.  loss_out (device float[3]) = (main + aux_weight * aux, main, aux), the last two
+ * unweighted; only an output: the backward never reads it, so the caller may scale it in place.
+ *
+ * fscnn_aux_head: head 0 CE (ignore_index), 1 Dice (smooth and dice_weight as
+ * fscnn_forward_loss_dice; plain Dice only, MixDiceLoss: focal_weight must be 0 -- the reference
+ * has no two-output Focal+Dice criterion -- and alpha / gamma are then unused; a non-zero
+ * focal_weight returns -2), 2 OHEM (ignore_index, thresh, min_kept, class_weight: device
+ * float[num_classes] or null, as fscnn_forward_loss_ohem); the fields of the other heads are
+ * ignored.  Pass the same values to the backward.
+ *
+ * head_ws (fscnn_aux_head_ws_bytes(plan, head) bytes, 256-B aligned, layout internal) is the one
+ * caller buffer that survives from the forward to the backward: the aux head's gradient planes,
+ * both heads' (mean, count) pairs / Dice sums and coefficient planes / OHEM planes, thresholds,
+ * counters (zeroed inside the run) and select scratch; the plan's own workspace sizes do not
+ * include it.  fscnn_aux_head_ws_bytes is negative (fscnn_last_error set) unless the plan is a
+ * train = 1 plan of an aux net and head is 0 .. 2.
+ *
+ * fscnn_backward_loss_aux takes d(loss) (device scalar); stage 0 scales the main head's gradient
+ * as fscnn_backward_loss does and the aux head's, times aux_weight, straight into the aux layer's
+ * low-resolution entry point (no upsample backward).  dx: the input gradient [N][3][H][W] in
+ * dx_dtype, or null (the Dice head does not form it: -1).  Null required pointers or inconsistent
+ * arguments return -1, more than 32 classes (Dice: fewer than 2) -2, both before anything is
+ * launched. */
+typedef struct fscnn_aux_head {
+  int head;                       /* 0 CE, 1 Dice, 2 OHEM */
+  float aux_weight;
+  long long ignore_index;         /* CE, OHEM */
+  float smooth, dice_weight, focal_weight, alpha, gamma; /* Dice (focal_weight 0) */
+  float thresh;                   /* OHEM */
+  long long min_kept;
+  const float* class_weight;
+} fscnn_aux_head;
+long long fscnn_aux_head_ws_bytes(const fscnn_plan* plan, int head);
+/* Debugging / parity, like fscnn_plan_buffer: byte offset in head_ws of head `which`'s (0 main,
+ * 1 aux) state `field` -- "pair" (float[2]: mean, count; Dice: float[1], the term), "stats"
+ * (Dice: double[4]), "prob" (OHEM: float[N*H*W]), "thr" (float[1]), "counts" (uint64[2]) -- or
+ * negative. */
+long long fscnn_aux_head_ws_offset(const fscnn_plan* plan, int head, const char* field, int which);
+int fscnn_forward_loss_aux(const fscnn_plan* plan, const void* x, int x_dtype,
+                           const long long* target, const fscnn_aux_head* h, float* loss_out,
+                           const float* params, float* running, long long* nbt, void* ws,
+                           void* head_ws, unsigned long long dropout_seed, float dropout_p,
+                           float momentum, void* stream);
+int fscnn_backward_loss_aux(const fscnn_plan* plan, const float* grad_loss,
+                            const fscnn_aux_head* h, const void* x, int x_dtype, void* dx,
+                            int dx_dtype, const float* params, float* grads, void* ws, void* bws,
+                            void* head_ws, unsigned long long dropout_seed, float dropout_p,
+                            int stage_from, int stage_to, void* stream);
+
 /* ---- fused blocks (inference) ---------------------------------------------------------------
  * fscnn_block_ir_fwd: one stride-1 LinearBottleneck (models/fast_scnn.py:95-115) with its three
  * BatchNorms folded (eval): y = BN_p(W_p * relu(BN_d(dw3x3(relu(BN_e(W_e * x)))))) (+ x when
