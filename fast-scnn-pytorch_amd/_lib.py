@@ -206,6 +206,23 @@ SIGNATURES = {
     "fscnn_dw3x3_dgrad_bn": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp,
                                      c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_vp,
                                      c_vp, c_vp, P_int, c_vp]),
+    "fscnn_dw3x3_wgrad_train": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int,
+                                        c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "fscnn_pw_fwd_train_route": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, P_int]),
+    "fscnn_pw_fwd_train": (c_int, [c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_vp,
+                                   c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                   c_float, c_vp, c_vp, c_vp, c_vp, c_int, P_int, P_int, c_vp]),
+    "fscnn_pw_wgrad_train": (c_int, [c_int, c_int, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp,
+                                     c_vp, c_vp, c_vp, c_vp, c_int, P_int, c_vp]),
+    "fscnn_pw_dgrad_train_route": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                           P_int]),
+    "fscnn_pw_dgrad_train": (c_int, [c_int, c_int, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int,
+                                     c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_int,
+                                     c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_int, c_float,
+                                     c_ull, c_ull, c_vp, c_int, P_int, P_int, c_vp]),
+    "fscnn_im2col3": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp]),
+    "fscnn_col2im3": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_int,
+                              c_vp]),
     "fscnn_block_ir_s2_fwd": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                       c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                       c_int, c_vp]),

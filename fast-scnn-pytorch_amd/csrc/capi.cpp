@@ -1692,6 +1692,302 @@ int fscnn_dw3x3_dgrad_bn(const void* dy, int dtype, int N, int H, int W, int C, 
   return dw_dgrad(d, dtype, S(stream));
 }
 
+int fscnn_dw3x3_wgrad_train(const void* x, const void* dy, int dtype, int N, int H, int W, int C,
+                            int stride, const float* x_scale, const float* x_shift, float* slab,
+                            float* dw, void* stream) {
+  if (!x || !dy || !slab || !dw || ((x_scale != nullptr) != (x_shift != nullptr))) {
+    set_error("fscnn_dw3x3_wgrad_train: null argument (x_scale and x_shift come together)");
+    return E_INVALID;
+  }
+  int rc = dw_train_check("fscnn_dw3x3_wgrad_train", dtype, N, H, W, C, stride);
+  if (rc) return rc;
+  // net.cpp Exec::dw_bwd, the weight-gradient half (X = act(u): x_scale / x_shift of a lazy input)
+  DwBwdArgs d{};
+  d.N = N; d.H = H; d.W = W; d.C = C; d.stride = stride;
+  d.Ho = (H - 1) / stride + 1; d.Wo = (W - 1) / stride + 1;
+  d.x = x; d.x_scale = x_scale; d.x_shift = x_shift; d.dy = dy; d.slab = slab;
+  rc = dw_wgrad(d, dtype, S(stream));
+  if (rc) return rc;
+  return dw_wgrad_reduce(slab, dw_wgrad_parts(N, d.Ho, d.Wo, C, dtype, stride), C, dw, S(stream));
+}
+
+// ---- the pointwise (1x1) train GEMM forms and the aux head's column kernels, in the executor's
+// form (tests/test_gpu_train_gemm.py)
+static int pw_geom_check(const char* who, int dtype, int M, int N, int K, int lda, int ldb,
+                         int ldc) {
+  if (!dt_ok(dtype)) {
+    set_error("%s: dtype %d", who, dtype);
+    return E_INVALID;
+  }
+  const int V = vec_w(dtype);
+  if (M < 1 || N < 1 || K < 1 || !ld_ok(lda, K, V) || !ld_ok(ldb, K, V) || ldc < N) {
+    set_error("%s: M=%d N=%d K=%d, row strides %d / %d / %d (the operands' >= K and a multiple "
+              "of %d, the output's >= N)", who, M, N, K, lda, ldb, ldc, V);
+    return E_INVALID;
+  }
+  return OK;
+}
+// 0: the streaming kernel (its last workgroup finishes the BN), 1: the tiled kernel finishing the
+// BN in its last workgroups, 2: the tiled kernel followed by the finalize launch
+static int pw_route(const GemmArgs& g, int dtype, int* records) {
+  int P;
+  const int ink = gemm_nt_tail_ink(g, dtype, &P);
+  if (records) *records = P;
+  return gemm_stream_ok(g, dtype) ? 0 : (ink ? 1 : 2);
+}
+
+// net.cpp Exec::pw (train branch) + gemm_fin + fin_args, field for field
+static GemmArgs pw_fwd_train_args(int M, int N, int K, const void* A, int lda,
+                                  const float* a_scale, const float* a_shift, const void* B,
+                                  int ldb, const float* bias, void* z, int ldc, float* part,
+                                  unsigned* counters, double* tsum, const BnFinalizeArgs& bn) {
+  GemmArgs g{};
+  g.M = M; g.N = N; g.K = K;
+  g.A = A; g.lda = lda; g.a_scale = a_scale; g.a_shift = a_shift;   // In x (act(u): lazy)
+  g.B = B; g.ldb = ldb; g.b_trans = 0;                              // Wg(c), ldb = K
+  g.scale = nullptr; g.shift = bias;                                // P(c.b)
+  g.C = z; g.ldc = ldc;                                             // W(u.z), u.C
+  g.part = part;                                                    // gemm_fin: Wf(u.part)
+  g.tail.counters = counters;                                       // pl.fcnt
+  g.tail.fwd = bn;                                                  // fin_args(u)
+  g.tail.fwd.part = part; g.tail.fwd.C = N;
+  g.tail.fwd.bias = nullptr;
+  g.tail.fwd.counters = counters;
+  g.tail.tsum = tsum;                                               // pl.tsum
+  return g;
+}
+
+static int pw_fwd_train_check(int M, int N, int K, int lda, int ldb, int ldc, int lazy, int dtype) {
+  const int rc = pw_geom_check("fscnn_pw_fwd_train", dtype, M, N, K, lda, ldb, ldc);
+  if (rc) return rc;
+  if (N > 1024 || (lazy && (K % vec_w(dtype) || K > 768))) {
+    set_error("fscnn_pw_fwd_train: N=%d K=%d (N <= 1024; a lazy operand needs K <= 768 and a "
+              "multiple of %d)", N, K, vec_w(dtype));
+    return E_INVALID;
+  }
+  return OK;
+}
+
+int fscnn_pw_fwd_train_route(int M, int N, int K, int lda, int ldc, int lazy, int dtype,
+                             int* records) {
+  if (pw_fwd_train_check(M, N, K, lda, lda, ldc, lazy, dtype)) return -1;  // (B's stride: no part)
+  static float f;     // host-side planning only reads which pointers are set
+  static unsigned u;
+  static double d;
+  const GemmArgs g = pw_fwd_train_args(M, N, K, &f, lda, lazy ? &f : nullptr, lazy ? &f : nullptr,
+                                       &f, lda, nullptr, &f, ldc, &f, &u, &d, BnFinalizeArgs{});
+  return pw_route(g, dtype, records);
+}
+
+int fscnn_pw_fwd_train(int M, int N, int K, const void* A, int lda, const float* a_scale,
+                       const float* a_shift, const void* B, int ldb, const float* bias, void* z,
+                       int ldc, float* part, unsigned* counters, double* tsum, const float* gamma,
+                       const float* beta, float* rmean, float* rvar, long long* nbt,
+                       float momentum, float* mean, float* invstd, float* scale, float* shift,
+                       int dtype, int* route, int* records, void* stream) {
+  if (!A || !B || !z || !part || !counters || !tsum || !gamma || !beta || !rmean || !rvar ||
+      !mean || !invstd || !scale || !shift || ((a_scale != nullptr) != (a_shift != nullptr))) {
+    set_error("fscnn_pw_fwd_train: null argument (a_scale and a_shift come together)");
+    return E_INVALID;
+  }
+  const int rc = pw_fwd_train_check(M, N, K, lda, ldb, ldc, a_scale != nullptr, dtype);
+  if (rc) return rc;
+  BnFinalizeArgs f{};  // fin_args(u); P is set by the finish that runs
+  f.gamma = gamma; f.beta = beta; f.rmean = rmean; f.rvar = rvar; f.nbt = nbt;
+  f.momentum = momentum;
+  f.mean = mean; f.invstd = invstd; f.scale = scale; f.shift = shift;
+  const GemmArgs g = pw_fwd_train_args(M, N, K, A, lda, a_scale, a_shift, B, ldb, bias, z, ldc,
+                                       part, counters, tsum, f);
+  int P;
+  const int rt = pw_route(g, dtype, &P);
+  if (route) *route = rt;
+  if (records) *records = P;
+  return gemm_nt(g, dtype, S(stream));
+}
+
+int fscnn_pw_wgrad_train(int M, int N, int K, const void* D, int ldd, const void* X, int ldx,
+                         const float* x_scale, const float* x_shift, float* slab, float* dW,
+                         float* bias_part, float* dbias, int dtype, int* splits, void* stream) {
+  if (!D || !X || !slab || !dW || ((x_scale != nullptr) != (x_shift != nullptr)) ||
+      ((bias_part != nullptr) != (dbias != nullptr))) {
+    set_error("fscnn_pw_wgrad_train: null argument (x_scale / x_shift and bias_part / dbias come "
+              "together)");
+    return E_INVALID;
+  }
+  if (!dt_ok(dtype)) {
+    set_error("fscnn_pw_wgrad_train: dtype %d", dtype);
+    return E_INVALID;
+  }
+  const int V = vec_w(dtype);
+  if (M < 1 || N < 1 || K < 1 || !ld_ok(ldd, N, V) || !ld_ok(ldx, K, V) || (x_scale && K % V)) {
+    set_error("fscnn_pw_wgrad_train: M=%d N=%d K=%d ldd=%d ldx=%d (ldd >= N, ldx >= K, both a "
+              "multiple of %d; a lazy X needs K a multiple of it too)", M, N, K, ldd, ldx, V);
+    return E_INVALID;
+  }
+  hipStream_t st = S(stream);
+  // net.cpp Exec::pw_bwd, the weight-gradient half: gemm_tn + reduce (+ colsum + reduce: c.b)
+  GemmTnArgs t{};
+  t.M = M; t.N = N; t.K = K; t.D = D; t.ldd = ldd; t.X = X; t.ldx = ldx;  // dz, In X
+  t.x_scale = x_scale; t.x_shift = x_shift;                               // X.sc, X.sh
+  const int s = gemm_tn_splits(M, N, K);
+  t.slab = slab;
+  if (splits) *splits = s;
+  int rc = gemm_tn(t, s, dtype, st);
+  if (rc) return rc;
+  rc = reduce_slabs(slab, s, (long long)N * K, (long long)N * K, dW, 0, st);
+  if (rc || !dbias) return rc;
+  rc = colsum(D, M, N, ldd, bias_part, dtype, st);
+  if (rc) return rc;
+  return reduce_slabs(bias_part, colsum_parts(M), N, N, dbias, 0, st);
+}
+
+// net.cpp Exec::pw_dgrad_args + set_btarget + bwd_tab, field for field
+static GemmArgs pw_dgrad_train_args(int M, int N, int K, const void* D, int ldd, const void* B,
+                                    int ldb, const void* R, int ldr, void* dX, int lddx,
+                                    const void* z, int ldz, const float* mean, const float* invstd,
+                                    const float* scale, const float* shift, int relu_mode,
+                                    float* part, unsigned* counters, double* tsum, float* dgamma,
+                                    float* dbeta, float* coef, float* tab, int drop_hw,
+                                    float drop_p, unsigned long long seed,
+                                    unsigned long long seed_add,
+                                    const unsigned long long* seed_slot) {
+  GemmArgs g{};
+  g.M = M; g.N = N; g.K = K; g.A = D; g.lda = ldd;           // dz
+  g.B = B; g.ldb = ldb; g.b_trans = 0;                       // WT(c), c.ldt
+  g.R = R; g.ldr = ldr;
+  g.C = dX; g.ldc = lddx;
+  g.bpart = part;                                            // pl.bnpart
+  g.bz = z; g.ldbz = ldz;                                    // W(u.z), u.C
+  g.bmean = mean; g.binvstd = invstd; g.bscale = scale; g.bshift = shift;
+  g.bmode = relu_mode;
+  g.tail.counters = counters;                                // pl.bcnt
+  g.tail.tsum = tsum;
+  g.tail.count = (double)M;                                  // bcount(u)
+  g.tail.dgamma = dgamma; g.tail.dbeta = dbeta; g.tail.coef = coef;
+  g.tail.tab.tab = tab;                                      // bwd_tab(u, mode == 2, slot)
+  g.tail.tab.scale = scale; g.tail.tab.shift = shift; g.tail.tab.mean = mean;
+  g.tail.tab.invstd = invstd;
+  g.tail.tab.relu = relu_mode == 2;
+  if (drop_hw > 0) {                                         // dro
+    g.drop_hw = drop_hw; g.drop_thr = dropout_threshold(drop_p); g.drop_p = drop_p;
+    g.drop_seed = seed; g.drop_seed_ptr = reinterpret_cast<const uint64_t*>(seed_slot);
+    g.drop_seed_add = seed_add;
+  }
+  return g;
+}
+
+static int pw_dgrad_train_check(int M, int N, int K, int ldd, int ldb, int ldr, int has_r,
+                                int lddx, int ldz, int relu_mode, int drop_hw, float drop_p,
+                                int dtype) {
+  const int rc = pw_geom_check("fscnn_pw_dgrad_train", dtype, M, N, K, ldd, ldb, lddx);
+  if (rc) return rc;
+  const int V = vec_w(dtype);
+  if ((relu_mode != 0 && relu_mode != 2) || N > 1024 || !ld_ok(ldz, N, V) ||
+      (has_r && !ld_ok(ldr, N, V))) {
+    set_error("fscnn_pw_dgrad_train: relu_mode %d N=%d ldz=%d ldr=%d (relu_mode 0 or 2, N <= 1024, "
+              "ldz / ldr >= N and a multiple of %d)", relu_mode, N, ldz, ldr, V);
+    return E_INVALID;
+  }
+  if (drop_hw < 0 || (drop_hw > 0 && (!(drop_p >= 0.f && drop_p < 1.f) || M % drop_hw))) {
+    set_error("fscnn_pw_dgrad_train: dropout hw %d p %g (0 <= p < 1, M a multiple of hw)", drop_hw,
+              (double)drop_p);
+    return E_INVALID;
+  }
+  return OK;
+}
+
+static int pw_dgrad_drop_check(const GemmArgs& g, int dtype) {
+  if (g.drop_hw && !gemm_stream_ok(g, dtype)) {
+    set_error("fscnn_pw_dgrad_train: an output dropout needs the streaming kernel, which does "
+              "not take M=%d N=%d K=%d in dtype %d", g.M, g.N, g.K, dtype);
+    return E_UNSUPPORTED;
+  }
+  return OK;
+}
+
+int fscnn_pw_dgrad_train_route(int M, int N, int K, int ldd, int lddx, int residual, int drop_hw,
+                               int dtype, int* records) {
+  if (pw_dgrad_train_check(M, N, K, ldd, ldd, lddx, residual, lddx, lddx, 0, drop_hw, 0.1f, dtype))
+    return -1;
+  static float f;     // host-side planning only reads which pointers are set
+  static unsigned u;
+  static double d;
+  const GemmArgs g = pw_dgrad_train_args(M, N, K, &f, ldd, &f, ldd, residual ? &f : nullptr, lddx,
+                                         &f, lddx, &f, lddx, &f, &f, &f, &f, 0, &f, &u, &d, &f,
+                                         &f, &f, &f, drop_hw, 0.1f, 0, 0, nullptr);
+  if (pw_dgrad_drop_check(g, dtype)) return -1;
+  return pw_route(g, dtype, records);
+}
+
+int fscnn_pw_dgrad_train(int M, int N, int K, const void* D, int ldd, const void* B, int ldb,
+                         const void* R, int ldr, void* dX, int lddx, const void* z, int ldz,
+                         const float* mean, const float* invstd, const float* scale,
+                         const float* shift, int relu_mode, float* part, unsigned* counters,
+                         double* tsum, float* dgamma, float* dbeta, float* coef, float* tab,
+                         int drop_hw, float drop_p, unsigned long long seed,
+                         unsigned long long seed_add, const unsigned long long* seed_slot,
+                         int dtype, int* route, int* records, void* stream) {
+  if (!D || !B || !dX || !z || !mean || !invstd || !scale || !shift || !part || !counters ||
+      !tsum || !dgamma || !dbeta || !coef || !tab || (uintptr_t)tab % 16) {
+    set_error("fscnn_pw_dgrad_train: null argument (or tab not 16-byte aligned)");
+    return E_INVALID;
+  }
+  int rc = pw_dgrad_train_check(M, N, K, ldd, ldb, ldr, R != nullptr, lddx, ldz, relu_mode,
+                                drop_hw, drop_p, dtype);
+  if (rc) return rc;
+  const GemmArgs g = pw_dgrad_train_args(M, N, K, D, ldd, B, ldb, R, ldr, dX, lddx, z, ldz, mean,
+                                         invstd, scale, shift, relu_mode, part, counters, tsum,
+                                         dgamma, dbeta, coef, tab, drop_hw, drop_p, seed, seed_add,
+                                         seed_slot);
+  rc = pw_dgrad_drop_check(g, dtype);
+  if (rc) return rc;
+  int P;
+  const int rt = pw_route(g, dtype, &P);
+  if (route) *route = rt;
+  if (records) *records = P;
+  return gemm_nt(g, dtype, S(stream));
+}
+
+// geometry shared by the aux head's column kernels
+static int col3_check(const char* who, int dtype, int N, int H, int W, int C, const void* x, int ldx,
+                      const void* col, int ldcol) {
+  if (!x || !col) {
+    set_error("%s: null argument", who);
+    return E_INVALID;
+  }
+  if (!dt_ok(dtype)) {
+    set_error("%s: dtype %d", who, dtype);
+    return E_INVALID;
+  }
+  if (N < 1 || H < 1 || W < 1 || C < 1 || ldx < C || ldcol < 9 * C) {
+    set_error("%s: N=%d H=%d W=%d C=%d, row strides %d (>= C) and %d (>= 9 C)", who, N, H, W, C,
+              ldx, ldcol);
+    return E_INVALID;
+  }
+  return OK;
+}
+
+int fscnn_im2col3(const void* x, int ldx, int dtype, int N, int H, int W, int C, void* col,
+                  int ldcol, void* stream) {
+  const int rc = col3_check("fscnn_im2col3", dtype, N, H, W, C, x, ldx, col, ldcol);
+  if (rc) return rc;
+  // net.cpp Exec::forward_aux
+  Im2ColArgs a{};
+  a.N = N; a.H = H; a.W = W; a.C = C; a.x = x; a.ldx = ldx; a.col = col; a.ldcol = ldcol;
+  return im2col3(a, dtype, S(stream));
+}
+
+int fscnn_col2im3(const void* dcol, int ldcol, int dtype, int N, int H, int W, int C, void* dx,
+                  int lddx, int accumulate, void* stream) {
+  const int rc = col3_check("fscnn_col2im3", dtype, N, H, W, C, dx, lddx, dcol, ldcol);
+  if (rc) return rc;
+  // net.cpp Exec::backward_aux (accumulate = 1 there)
+  Col2ImArgs a{};
+  a.N = N; a.H = H; a.W = W; a.C = C; a.dcol = dcol; a.ldcol = ldcol; a.dx = dx; a.lddx = lddx;
+  a.accumulate = accumulate != 0;
+  return col2im3(a, dtype, S(stream));
+}
+
 int fscnn_block_ir_fwd(const void* x, int ldx, int dtype, int N, int H, int W, int cin, int expand,
                        int cout, const void* w_expand, const float* w_dw, const void* w_project,
                        const float* scale_e, const float* shift_e, const float* scale_d,

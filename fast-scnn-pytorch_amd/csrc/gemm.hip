@@ -520,6 +520,32 @@ int gemm_nt_parts(const GemmArgs& a, int dtype) {
   return use_stream(a, dtype) ? gemm_stream_parts(a, dtype) : gemm_parts(a.M);
 }
 
+// column tiles (of 16) per workgroup of the tiled kernel
+static int tiled_nt(const GemmArgs& a) {
+  int nt = pick_nt(a.N);
+  // small-M problems (the 16 K-row bottleneck2/3 projects and expand dgrads: 128 row tiles)
+  // split the columns down to NT = 2 so ~512 workgroups (two per CU, eight waves) are in flight:
+  // measured r04 5.965-5.976 ms/step vs 6.001-6.007 at a minimum grid of 256 and 6.016-6.018 at
+  // 1024
+  constexpr int min_tiles = 512;
+  while ((long long)cdiv(a.M, G_BM) * cdiv(a.N, 16 * nt) < min_tiles &&
+         (nt == 8 || nt == 6 || nt == 4 || nt == 3))
+    nt = nt == 3 ? 2 : nt / 2;
+  return nt;
+}
+
+// tiled path: the BN finish runs in the kernel's last workgroups (bn_finish.hpp tail_finish)
+// when the records fit its counters; otherwise as its own fold + finalize launch
+static bool tiled_tail_ink(const GemmArgs& a, int nt, bool stream) {
+  return !stream && a.tail.counters && !a.b_trans && a.tail.tsum && a.N <= TAIL_CMAX &&
+         tail_fits(gemm_parts(a.M), cdiv(a.N, 16 * nt));
+}
+
+int gemm_nt_tail_ink(const GemmArgs& a, int dtype, int* P) {
+  if (P) *P = gemm_nt_parts(a, dtype);
+  return tiled_tail_ink(a, tiled_nt(a), use_stream(a, dtype)) ? 1 : 0;
+}
+
 template <typename T, bool BT, bool BS, bool AT, bool X3, bool TL>
 static void launch_nt_tl(const GemmArgs& a, int nt, dim3 grid, size_t shm, hipStream_t st) {
   switch (nt) {
@@ -576,15 +602,7 @@ int gemm_nt(const GemmArgs& a, int dtype, hipStream_t st) {
     set_error("gemm_nt: statistics with residual not supported");
     return E_UNSUPPORTED;
   }
-  int nt = pick_nt(a.N);
-  // small-M problems (the 16 K-row bottleneck2/3 projects and expand dgrads: 128 row tiles)
-  // split the columns down to NT = 2 so ~512 workgroups (two per CU, eight waves) are in flight:
-  // measured r04 5.965-5.976 ms/step vs 6.001-6.007 at a minimum grid of 256 and 6.016-6.018 at
-  // 1024
-  constexpr int min_tiles = 512;
-  while ((long long)cdiv(a.M, G_BM) * cdiv(a.N, 16 * nt) < min_tiles &&
-         (nt == 8 || nt == 6 || nt == 4 || nt == 3))
-    nt = nt == 3 ? 2 : nt / 2;
+  const int nt = tiled_nt(a);
   const double E = dtype == DT_F32 ? 4.0 : 2.0;
   const double M = a.M, N = a.N, K = a.K;
   const bool at = a.a_scale != nullptr;
@@ -611,11 +629,9 @@ int gemm_nt(const GemmArgs& a, int dtype, hipStream_t st) {
   const bool stream = use_stream(a, dtype);
   GemmArgs as = a;
   as.stamps = stamp_region();
-  // tiled path: the BN finish runs in the kernel's last workgroups (bn_finish.hpp tail_finish)
-  // when the records fit its counters; otherwise as its own fold + finalize launch below
+  // tiled path: the BN finish in the kernel (tiled_tail_ink) or as its own launch below
   GemmArgs b = as;
-  b.tail_ink = !stream && a.tail.counters && !a.b_trans &&
-               a.tail.tsum && a.N <= TAIL_CMAX && tail_fits(gemm_parts(a.M), cdiv(a.N, 16 * nt));
+  b.tail_ink = tiled_tail_ink(a, nt, stream);
   int rc;
   {
     ProfScope ps(PK_GEMM_NT, st,

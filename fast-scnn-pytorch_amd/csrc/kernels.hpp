@@ -627,6 +627,10 @@ bool gemm_stream_ok(const GemmArgs& a, int dtype);
 int gemm_stream(const GemmArgs& a, int dtype, hipStream_t st);  // streaming gemm_nt (gemm_stream.hip)
 int gemm_stream_parts(const GemmArgs& a, int dtype);  // its workgroups per column group
 int gemm_nt_parts(const GemmArgs& a, int dtype);      // BN records gemm_nt(a) writes
+// whether gemm_nt(a) takes its tiled kernel AND that kernel finishes the BN of a.tail itself
+// (else: the streaming kernel's own finish, or the tiled kernel plus a finalize launch); *P: the
+// record count, gemm_nt_parts(a)
+int gemm_nt_tail_ink(const GemmArgs& a, int dtype, int* P);
 int gemm_tn_splits(int M, int N, int K);
 int gemm_tn(GemmTnArgs a, int splits, int dtype, hipStream_t st);
 // slab is consumed (folded in place)

@@ -835,6 +835,70 @@ int fscnn_dw3x3_dgrad_bn(const void* dy, int dtype, int N, int H, int W, int C, 
                          const float* invstd, const float* scale, const float* shift,
                          int relu_mode, float* part, unsigned* counters, double* tsum,
                          float* dgamma, float* dbeta, float* coef, int* in_kernel, void* stream);
+/* fscnn_dw3x3_wgrad over a lazy input: x is a raw conv output and the operand is
+ * relu(x*x_scale + x_shift) rounded to the storage type (x_scale / x_shift together, or both null:
+ * x itself); padding stays zero.  slab: fscnn_dw3x3_wgrad_slab_floats floats; dw [C][3][3]. */
+int fscnn_dw3x3_wgrad_train(const void* x, const void* dy, int dtype, int N, int H, int W, int C,
+                            int stride, const float* x_scale, const float* x_shift, float* slab,
+                            float* dw, void* stream);
+
+/* ---- the pointwise (1x1) conv of a train step, in the executor's three GEMM forms
+ * (tests/test_gpu_train_gemm.py).  Shared scratch: counters 512 zeroed uint32 (left zero), tsum
+ * 32*3*1024 doubles.  *route (nullable) reports which kernel and which BatchNorm finish ran:
+ * 0 the streaming kernel (its last workgroup finishes), 1 the tiled kernel finishing in its own
+ * last workgroups, 2 the tiled kernel followed by a finalize launch; *records (nullable): the
+ * BN records written (<= ceil(M/128)).  The *_route calls answer the same two questions on the
+ * host alone (no launch; -1 on arguments the call itself would refuse).
+ *
+ * fwd_train: z[M][N] (ldc) = a[M][K] . B^T (+ bias[n]), B [N][K] (ldb), a = A (lda) or, with
+ * a_scale / a_shift (together; K <= 768, K % V == 0), relu(A*a_scale[k] + a_shift[k]) rounded to
+ * the storage type (bn_apply's output, never stored).  Plus the batch statistics of the STORED z,
+ * finished in the same call: mean, invstd, scale = gamma*invstd, shift = beta - mean*scale, the
+ * running statistics (momentum; unbiased variance) and *nbt += 1 (nullable).  part: room for
+ * ceil(M/128)*3*N floats. */
+int fscnn_pw_fwd_train_route(int M, int N, int K, int lda, int ldc, int lazy, int dtype,
+                             int* records);
+int fscnn_pw_fwd_train(int M, int N, int K, const void* A, int lda, const float* a_scale,
+                       const float* a_shift, const void* B, int ldb, const float* bias, void* z,
+                       int ldc, float* part, unsigned* counters, double* tsum, const float* gamma,
+                       const float* beta, float* rmean, float* rvar, long long* nbt,
+                       float momentum, float* mean, float* invstd, float* scale, float* shift,
+                       int dtype, int* route, int* records, void* stream);
+/* wgrad_train: dW[N][K] = sum_m D[m][n] x[m][k], x = X or its lazy BN+ReLU (x_scale / x_shift as
+ * above), and, when dbias is given, dbias[n] = sum_m D[m][n] (bias_part: ceil(M/1024)*N floats,
+ * given together with dbias).  slab: fscnn_pw_wgrad_slab_floats floats; *splits (nullable): the
+ * row splits, each of ceil(ceil(M/splits)/64)*64 rows. */
+int fscnn_pw_wgrad_train(int M, int N, int K, const void* D, int ldd, const void* X, int ldx,
+                         const float* x_scale, const float* x_shift, float* slab, float* dW,
+                         float* bias_part, float* dbias, int dtype, int* splits, void* stream);
+/* dgrad_train: fscnn_pw_dgrad_bnbwd's call (same arguments, same sums) plus
+ *  - tab [N][8] (16-byte aligned): that BN's backward as a per-channel operand transform,
+ *    dz = al*mask*dy + gz*z + be with mask = (z*sc + sh > 0); tab[n] = (al, be, gz, sc, sh, ...),
+ *    al = scale, gz = -scale*coef1*invstd, be = -scale*coef0 - gz*mean, (sc, sh) = the forward
+ *    (scale, shift) in relu_mode 2 and (0, 1) in relu_mode 0;
+ *  - an output dropout (drop_hw > 0: pixels per image, M % drop_hw == 0): the stored dX is
+ *    fscnn_dropout's keep ? round(dX) / (1 - p) : 0 with the mask of NCHW index
+ *    ((m / hw)*N + n)*hw + m % hw and seed (or *seed_slot) + seed_add, and the BN sums are those
+ *    of the dropped dX.  Streaming kernel only (16-bit K <= 32, fp32 K <= 16, M >= 4096):
+ *    refused otherwise. */
+int fscnn_pw_dgrad_train_route(int M, int N, int K, int ldd, int lddx, int residual, int drop_hw,
+                               int dtype, int* records);
+int fscnn_pw_dgrad_train(int M, int N, int K, const void* D, int ldd, const void* B, int ldb,
+                         const void* R, int ldr, void* dX, int lddx, const void* z, int ldz,
+                         const float* mean, const float* invstd, const float* scale,
+                         const float* shift, int relu_mode, float* part, unsigned* counters,
+                         double* tsum, float* dgamma, float* dbeta, float* coef, float* tab,
+                         int drop_hw, float drop_p, unsigned long long seed,
+                         unsigned long long seed_add, const unsigned long long* seed_slot,
+                         int dtype, int* route, int* records, void* stream);
+/* The aux head's 3x3 conv as columns (pad 1, stride 1), x NHWC [N][H][W] (ldx >= C):
+ * col[m][c*9 + kh*3 + kw] = x[n][h+kh-1][w+kw-1][c] or 0 (ldcol >= 9 C; columns past 9 C are not
+ * written), and its transpose dx[m][c] (+)= sum_{kh,kw} dcol[n][h+1-kh][w+1-kw][c*9 + kh*3 + kw]
+ * (accumulate: added to the stored dx). */
+int fscnn_im2col3(const void* x, int ldx, int dtype, int N, int H, int W, int C, void* col,
+                  int ldcol, void* stream);
+int fscnn_col2im3(const void* dcol, int ldcol, int dtype, int N, int H, int W, int C, void* dx,
+                  int lddx, int accumulate, void* stream);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,10 @@ NUL = None
 
 NEW = ["fscnn_bn_apply", "fscnn_bn_bwd", "fscnn_ppm_branches_ok", "fscnn_ppm_branches_fwd",
        "fscnn_ppm_branches_bwd", "fscnn_ppm_up_fwd", "fscnn_ppm_up_bwd", "fscnn_dropout",
-       "fscnn_dw3x3_parts", "fscnn_dw3x3_fwd_train", "fscnn_dw3x3_dgrad_bn"]
+       "fscnn_dw3x3_parts", "fscnn_dw3x3_fwd_train", "fscnn_dw3x3_dgrad_bn",
+       "fscnn_dw3x3_wgrad_train", "fscnn_pw_fwd_train_route", "fscnn_pw_fwd_train",
+       "fscnn_pw_wgrad_train", "fscnn_pw_dgrad_train_route", "fscnn_pw_dgrad_train",
+       "fscnn_im2col3", "fscnn_col2im3"]
 
 
 def test_new_entry_points_resolve():
@@ -69,6 +72,36 @@ def dw_fwd(C=32, stride=1, in_scale=NUL, in_shift=NUL, tsum=X, dt=BF16):
 def dw_dgrad(C=32, stride=1, mode=0, shift=X, z=X, dt=BF16):
     return ("fscnn_dw3x3_dgrad_bn", (X, dt, 2, 17, 23, C, stride, X, X, z, X, X, X, shift, mode,
                                      X, X, X, X, X, X, None, NUL))
+
+
+def dw_wgrad(C=32, stride=1, xs=NUL, xh=NUL, dw=X, dt=BF16):
+    return ("fscnn_dw3x3_wgrad_train", (X, X, dt, 2, 17, 23, C, stride, xs, xh, X, dw, NUL))
+
+
+def pw_fwd(M=300, N=96, K=576, A=X, lda=576, a_sc=NUL, a_sh=NUL, ldb=576, ldc=96, tsum=X, mean=X,
+           dt=BF16):
+    return ("fscnn_pw_fwd_train", (M, N, K, A, lda, a_sc, a_sh, X, ldb, NUL, X, ldc, X, X, tsum, X, X,
+                                   X, X, NUL, 0.1, mean, X, X, X, dt, None, None, NUL))
+
+
+def pw_wgrad(M=777, N=19, K=128, D=X, ldd=24, ldx=128, xs=NUL, xh=NUL, bias_part=NUL, dbias=NUL,
+             dt=BF16):
+    return ("fscnn_pw_wgrad_train", (M, N, K, D, ldd, X, ldx, xs, xh, X, X, bias_part, dbias, dt,
+                                     None, NUL))
+
+
+def pw_dgrad(M=4514, N=128, K=19, ldd=24, ldb=24, R=NUL, ldr=0, lddx=128, ldz=128, mode=2, tab=X,
+             coef=X, hw=0, p=0.1, dt=BF16):
+    return ("fscnn_pw_dgrad_train", (M, N, K, X, ldd, X, ldb, R, ldr, X, lddx, X, ldz, X, X, X, X, mode,
+                                     X, X, X, X, X, coef, tab, hw, p, 7, 0, NUL, dt, None, None, NUL))
+
+
+def im2col(x=X, ldx=64, ldcol=576, C=64, dt=BF16):
+    return ("fscnn_im2col3", (x, ldx, dt, 2, 5, 7, C, X, ldcol, NUL))
+
+
+def col2im(dx=X, lddx=64, ldcol=576, H=5, dt=BF16):
+    return ("fscnn_col2im3", (X, ldcol, dt, 2, H, 7, 64, dx, lddx, 1, NUL))
 
 
 REFUSED = {
@@ -130,6 +163,61 @@ REFUSED = {
     "dw_dgrad_bn C % V (fp32)": dw_dgrad(C=30, dt=F32),
     "dw_dgrad_bn null z": dw_dgrad(z=NUL),
     "dw_dgrad_bn stride 0": dw_dgrad(stride=0),
+    "dw_wgrad_train x_scale without x_shift": dw_wgrad(xs=X),
+    "dw_wgrad_train x_shift without x_scale": dw_wgrad(xh=X),
+    "dw_wgrad_train null dw": dw_wgrad(dw=NUL),
+    "dw_wgrad_train C % V": dw_wgrad(C=36),
+    "dw_wgrad_train stride 3": dw_wgrad(stride=3),
+    "dw_wgrad_train dtype": dw_wgrad(dt=3),
+    "pw_fwd_train null A": pw_fwd(A=NUL),
+    "pw_fwd_train null mean": pw_fwd(mean=NUL),
+    "pw_fwd_train no team sums": pw_fwd(tsum=NUL),
+    "pw_fwd_train a_scale without a_shift": pw_fwd(a_sc=X),
+    "pw_fwd_train a_shift without a_scale": pw_fwd(a_sh=X),
+    "pw_fwd_train lda < K": pw_fwd(lda=568),
+    "pw_fwd_train lda % V": pw_fwd(lda=580),
+    "pw_fwd_train ldb % V (fp32: 4)": pw_fwd(ldb=578, dt=F32),
+    "pw_fwd_train ldc < N": pw_fwd(ldc=64),
+    "pw_fwd_train lazy K % V": pw_fwd(K=572, a_sc=X, a_sh=X, dt=BF16),
+    "pw_fwd_train lazy K > 768": pw_fwd(K=776, lda=776, ldb=776, a_sc=X, a_sh=X),
+    "pw_fwd_train N > 1024": pw_fwd(N=1032, ldc=1032),
+    "pw_fwd_train M = 0": pw_fwd(M=0),
+    "pw_fwd_train dtype": pw_fwd(dt=3),
+    "pw_wgrad_train null D": pw_wgrad(D=NUL),
+    "pw_wgrad_train x_scale without x_shift": pw_wgrad(xs=X),
+    "pw_wgrad_train dbias without its scratch": pw_wgrad(dbias=X),
+    "pw_wgrad_train scratch without dbias": pw_wgrad(bias_part=X),
+    "pw_wgrad_train ldd < N": pw_wgrad(ldd=16),
+    "pw_wgrad_train ldd % V": pw_wgrad(ldd=20),
+    "pw_wgrad_train ldx < K": pw_wgrad(ldx=120),
+    "pw_wgrad_train lazy K % V": pw_wgrad(K=124, xs=X, xh=X),
+    "pw_wgrad_train dtype": pw_wgrad(dt=-1),
+    "pw_dgrad_train null tab": pw_dgrad(tab=NUL),
+    "pw_dgrad_train null coef": pw_dgrad(coef=NUL),
+    "pw_dgrad_train tab alignment": pw_dgrad(tab=_lib.c_vp(0x1004)),
+    "pw_dgrad_train relu_mode 1": pw_dgrad(mode=1),
+    "pw_dgrad_train ldd < K": pw_dgrad(ldd=16),
+    "pw_dgrad_train ldb % V": pw_dgrad(ldb=28),
+    "pw_dgrad_train lddx < N": pw_dgrad(lddx=64),
+    "pw_dgrad_train ldz % V": pw_dgrad(ldz=132),
+    "pw_dgrad_train residual stride": pw_dgrad(R=X, ldr=64),
+    "pw_dgrad_train dropout p = 1": pw_dgrad(hw=2257, p=1.0),
+    "pw_dgrad_train dropout M % hw": pw_dgrad(hw=2000),
+    "pw_dgrad_train dropout hw < 0": pw_dgrad(hw=-1),
+    "pw_dgrad_train dropout below the streaming kernel's M": pw_dgrad(M=300, hw=100),
+    "pw_dgrad_train dropout, two k-steps": pw_dgrad(K=48, ldd=48, ldb=48, hw=2257),
+    "pw_dgrad_train dropout, fp32 K = 19": pw_dgrad(hw=2257, dt=F32),
+    "pw_dgrad_train dtype": pw_dgrad(dt=3),
+    "im2col3 null x": im2col(x=NUL),
+    "im2col3 ldx < C": im2col(ldx=32),
+    "im2col3 ldcol < 9 C": im2col(ldcol=512),
+    "im2col3 C = 0": im2col(C=0, ldx=0, ldcol=0),
+    "im2col3 dtype": im2col(dt=3),
+    "col2im3 null dx": col2im(dx=NUL),
+    "col2im3 lddx < C": col2im(lddx=32),
+    "col2im3 ldcol < 9 C": col2im(ldcol=575),
+    "col2im3 H = 0": col2im(H=0),
+    "col2im3 dtype": col2im(dt=-1),
 }
 
 
@@ -166,3 +254,47 @@ def test_dw3x3_parts_counts_and_refusal():
     assert lib.fscnn_dw3x3_parts(2, 17, 23, 36, 1, BF16, 0) == -1
     assert lib.fscnn_dw3x3_parts(2, 17, 23, 32, 3, BF16, 0) == -1
     assert b"fscnn_dw3x3_parts" in lib.fscnn_last_error()
+
+
+# (M, N, K, ldc) -> route of fscnn_pw_fwd_train: 0 streaming kernel, 1 tiled kernel finishing its
+# BN itself, 2 tiled kernel + finalize launch (the shapes of tests/test_gpu_train_gemm.py)
+FWD_ROUTES = [((4133, 48, 32, 48), 0), ((4133, 64, 48, 64), 0), ((4133, 128, 128, 128), 0),
+              ((4133, 64, 384, 64), 1), ((4133, 128, 768, 128), 1), ((4133, 96, 576, 96), 1),
+              ((300, 96, 576, 96), 1), ((129, 64, 384, 64), 1), ((4133, 19, 128, 24), 1),
+              ((300, 576, 96, 576), 2),
+              # N = 384, K = 64 never takes route 2: 12 column groups fit the in-kernel finish
+              # below M = 4096, the streaming kernel takes it from there
+              ((300, 384, 64, 384), 1), ((4095, 384, 64, 384), 1), ((4096, 384, 64, 384), 0),
+              ((65539, 384, 64, 384), 0)]
+
+
+def test_pw_fwd_train_routes():
+    lib = _lib.load()
+    for (M, N, K, ldc), route in FWD_ROUTES:
+        for dt in (F32, BF16, F16):
+            for lazy in (0, 1):
+                recs = _lib.c_int(-1)
+                got = lib.fscnn_pw_fwd_train_route(M, N, K, K + 8, ldc, lazy, dt, _lib.ctypes.byref(recs))
+                assert got == route, (M, N, K, dt, lazy, got)
+                assert 1 <= recs.value <= (M + 127) // 128
+                if route:
+                    assert recs.value == (M + 127) // 128   # the tiled kernel: one record per tile
+    assert lib.fscnn_pw_fwd_train_route(300, 96, 572, 576, 96, 1, BF16, None) == -1
+    assert b"fscnn_pw_fwd_train" in lib.fscnn_last_error()
+
+
+def test_pw_dgrad_train_routes():
+    lib = _lib.load()
+    recs = _lib.c_int(-1)
+    r = _lib.ctypes.byref(recs)
+    # the classifier dgrad with its dropout: one k-step, streaming, 16-bit (fp32: K <= 16 only)
+    for dt in (BF16, F16):
+        assert lib.fscnn_pw_dgrad_train_route(2 * 37 * 61, 128, 19, 24, 128, 0, 37 * 61, dt, r) == 0
+        assert lib.fscnn_pw_dgrad_train_route(2 * 37 * 61, 128, 19, 24, 128, 1, 37 * 61, dt, r) == 0
+        assert lib.fscnn_pw_dgrad_train_route(4133, 64, 128, 136, 64, 0, 0, dt, r) == 0
+    assert lib.fscnn_pw_dgrad_train_route(2 * 37 * 61, 128, 19, 24, 128, 0, 37 * 61, F32, r) == -1
+    assert b"fscnn_pw_dgrad_train" in lib.fscnn_last_error()
+    for dt in (F32, BF16, F16):
+        assert lib.fscnn_pw_dgrad_train_route(3 * 37 * 37, 128, 2, 8, 128, 0, 37 * 37, dt, r) == 0
+    assert lib.fscnn_pw_dgrad_train_route(4133, 64, 128, 132, 64, 0, 0, F32, r) == 1
+    assert recs.value == 33
