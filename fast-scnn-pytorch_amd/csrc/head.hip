@@ -1,139 +1,54 @@
-// Fused training head: the final F.interpolate(bilinear, align_corners=True) of the logits
-// (models/fast_scnn.py:40) + nn.CrossEntropyLoss(ignore_index=-1) (utils/loss.py:103-124) and
-// its gradient back to the LOW-resolution logits, in one pass that never writes full-resolution
-// logits (8 x 19 x 1024 x 2048 would be 637 MB bf16 written, read, re-written and re-read by the
-// unfused path).
-//
-// Layout of the work: workgroup (hl, n) owns the full-resolution pixels whose bilinear row tap
-// i0(h) is low-res row hl, across the whole width; thread t owns the pixels whose column tap
-// i0(w) is low-res column t.  Every pixel is therefore computed exactly once (no halo).  A pixel
-// touches cells (i0h|i1h) x (i0w|i1w); its four contributions are accumulated in registers:
-// (hl, t) and (hl, t+1) belong to the workgroup's own row, (hl+1, *) is its row spill.  At the
-// end thread t adds its neighbour's (hl, t) share in a fixed order and writes the own-row plane;
-// the spill plane (row hl+1) is written separately and summed in ce_head_scale, so the result is
-// deterministic without atomics.  The two low-res logit rows the workgroup interpolates from are
-// staged in LDS (odd row stride: conflict-free per-thread class walks).
-#include "kernels.hpp"
+// The fused training loss heads: upsample + criterion + gradient to the low-resolution logits in
+// one pass (8 x 19 x 1024 x 2048 full-resolution logits would be 637 MB bf16 written, read,
+// re-written and re-read by the unfused path).  The work layout all four kernels share -- tile
+// geometry, logit staging, target rows, tap accumulation, chunk epilogue, block reduce -- is
+// head_tile.hpp; a kernel here holds only its own per-pixel arithmetic.
+#include <type_traits>
+
+#include "head_tile.hpp"
 
 namespace fscnn {
 
-constexpr int HD_T = 256;
-constexpr int HD_CMAX = 32;
-constexpr int HD_TMAX = 2048;  // max full-res row width whose targets are staged in LDS
-constexpr float HD_LOG2E = 1.4426950408889634f;
-constexpr float HD_LN2 = 0.6931471805599453f;
 constexpr int HD_PD = 4;  // int8 target rows in flight per thread (ce_head2_kernel)
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ int hd_first_ge(int i, int Lin, int Lout, float sc) {
-  int lo = 0, hi = Lout;
-  while (lo < hi) {
-    int mid = (lo + hi) >> 1;
-    if (ac_lerp(mid, Lin, Lout, sc).i0 >= i) hi = mid;
-    else lo = mid + 1;
-  }
-  return lo;
-}
-
+// nn.CrossEntropyLoss(ignore_index=-1) (utils/loss.py:103-124) with a per-pixel softmax: fp32
+// plans, and 16-bit plans with class counts other than 19 and 2.
 template <typename T, int CT, bool EXACT>
 __global__ __launch_bounds__(HD_T) void ce_head_kernel(CeHeadArgs a) {
   constexpr int SL = (CT % 2 == 0) ? CT + 1 : CT;  // odd LDS stride per column
+  constexpr int CP = (CT + 1) / 2;
   __shared__ float s_L[2 * (HD_T + 1) * SL];
   __shared__ float s_carry[2 * CT];
   __shared__ signed char s_t[2 * HD_TMAX];
-  __shared__ float s_r1[HD_T], s_r2[HD_T];
-  const int tid = threadIdx.x;
-  const int hl = blockIdx.x, n = blockIdx.y;
-  const int Hl = a.Hl, Wl = a.Wl, H = a.H, W = a.W, ldl = a.ldl;
+  __shared__ float s_r[2][HD_T];
+  const HeadTile tl(a.Hl, a.Wl, a.H, a.W);
+  const int tid = tl.tid, ldl = a.ldl;
   const int Cm = EXACT ? CT : a.C;
-  const float sh = ac_scale(Hl, H), sw = ac_scale(Wl, W);
-  const int h_lo = hd_first_ge(hl, Hl, H, sh), h_hi = hd_first_ge(hl + 1, Hl, H, sh);
-  const int hl1 = min(hl + 1, Hl - 1);
-  const T* lg = (const T*)a.logits + (size_t)n * Hl * Wl * ldl;
-  float* g0 = a.g_raw;                              // own-row plane
-  float* g1 = a.g_raw + (size_t)a.N * Hl * Wl * ldl;  // spill plane (row hl+1)
-  const long long* tgt = a.target + (size_t)n * H * W;
+  const T* lg = (const T*)a.logits + tl.image(ldl);
+  float* g1 = tl.spill_plane(a.g_raw, a.N, ldl);
   float loss = 0.f, cnt = 0.f;
-  if (tid < 2 * CT) s_carry[tid] = 0.f;
-  if (hl == 0) {  // nothing spills into row 0
-    for (int i = tid; i < Wl * ldl; i += HD_T) g1[(size_t)n * Hl * Wl * ldl + i] = 0.f;
-  }
-  for (int cb = 0; cb < Wl; cb += HD_T) {
-    __syncthreads();
-    // ---- stage low-res rows hl, hl1 for columns [cb, cb + HD_T] (clamped) -----------------
-    for (int i = tid; i < 2 * (HD_T + 1) * CT; i += HD_T) {
-      const int c = i % CT, jr = i / CT;
-      const int j = jr % (HD_T + 1), r = jr / (HD_T + 1);
-      const int col = min(cb + j, Wl - 1);
-      const int row = r ? hl1 : hl;
-      // staged in log2 units (x log2 e): the softmax below runs on v_exp_f32 (2^x) directly
-      s_L[(r * (HD_T + 1) + j) * SL + c] =
-          c < Cm ? ld1(lg + ((size_t)row * Wl + col) * ldl + c) * HD_LOG2E : 0.f;
-    }
-    __syncthreads();
-    const int t = cb + tid;
-    const bool active = t < Wl;
-    // a0[c] = (acc00, acc01): own row, columns t / t+1; a1[c] = (acc10, acc11): row hl+1
+  hd_carry_zero<CT>(s_carry, tid);
+  tl.zero_spill_row0(g1, ldl);
+  for (int cb = 0; cb < tl.Wl; cb += HD_T) {
+    hd_stage_rows_f32<T, CT, SL>(s_L, lg, tl, cb, Cm, ldl);
+    const HeadCols cl(tl, cb);
     f32x2 a0[CT], a1[CT];
 #pragma unroll
     for (int c = 0; c < CT; ++c) a0[c] = a1[c] = f32x2{0.f, 0.f};
-    // the full-resolution target rows are loaded by the whole workgroup with coalesced int64
-    // loads (next row prefetched into registers during the current row) and kept in LDS as int8
-    // class indices (-1 = ignored); all threads run the row loop (inactive columns: no pixels)
-    const int w_lo = active ? hd_first_ge(t, Wl, W, sw) : 0;
-    const int w_hi = active ? hd_first_ge(t + 1, Wl, W, sw) : 0;
-    const bool lds_t = W <= HD_TMAX;
-    constexpr int TPT = HD_TMAX / HD_T;
-    int tnext[TPT];
-    auto load_trow = [&](int h) {
-      const long long* tr = tgt + (size_t)h * W;
-#pragma unroll
-      for (int k = 0; k < TPT; ++k) {
-        const int w = tid + HD_T * k;
-        const long long tg = tr[w < W ? w : 0];
-        tnext[k] = (w < W && tg != a.ignore_index && tg >= 0 && tg < Cm) ? (int)tg : -1;
-      }
-    };
-    if (lds_t && h_lo < h_hi) load_trow(h_lo);
+    HdTargetRows<HdIgnoreAware, false> tr(tl, a.target, nullptr, s_t, HdIgnoreAware{a.ignore_index},
+                                          Cm, tl.W <= HD_TMAX);
+    tr.start(tl.h_lo, tl.h_hi);
     const float* L0 = &s_L[tid * SL];
     const float* L1 = &s_L[((HD_T + 1) + tid) * SL];
-    for (int h = h_lo; h < h_hi; ++h) {
-      signed char* trow_s = s_t + (h & 1) * HD_TMAX;
-      if (lds_t) {
-#pragma unroll
-        for (int k = 0; k < TPT; ++k)
-          if (tid + HD_T * k < W) trow_s[tid + HD_T * k] = (signed char)tnext[k];
-        __syncthreads();
-        if (h + 1 < h_hi) load_trow(h + 1);
-      }
-      if (active) {
-        const Lerp lh = ac_lerp(h, Hl, H, sh);
-        // class pairs (v_pk_* f32): v0 = the row-interpolated low-res logits of column t and
-        // dv = (column t+1) - v0 (log2 units), padded to an even class count with zeros; a
-        // pixel's logit is then ONE packed fma, v0 + lw.l1 * dv
-        constexpr int CP = (CT + 1) / 2;
+    for (int h = tl.h_lo; h < tl.h_hi; ++h) {
+      tr.commit(h, tl.h_hi);
+      if (cl.active) {
+        const Lerp lh = ac_lerp(h, tl.Hl, tl.H, tl.sh);
         f32x2 v0[CP], dv[CP];
-        const f32x2 h0 = {lh.l0, lh.l0}, h1 = {lh.l1, lh.l1};
-#pragma unroll
-        for (int p = 0; p < CP; ++p) {
-          const int c = 2 * p, c1 = c + 1 < CT ? c + 1 : c;
-          const f32x2 l00 = {L0[c], c + 1 < CT ? L0[c1] : 0.f};
-          const f32x2 l10 = {L1[c], c + 1 < CT ? L1[c1] : 0.f};
-          const f32x2 l01 = {L0[SL + c], c + 1 < CT ? L0[SL + c1] : 0.f};
-          const f32x2 l11 = {L1[SL + c], c + 1 < CT ? L1[SL + c1] : 0.f};
-          v0[p] = __builtin_elementwise_fma(h1, l10, h0 * l00);
-          dv[p] = __builtin_elementwise_fma(h1, l11, h0 * l01) - v0[p];
-        }
-        const long long* trow = tgt + (size_t)h * W;
-        for (int w = w_lo; w < w_hi; ++w) {
-          const Lerp lw = ac_lerp(w, Wl, W, sw);
-          int ti;
-          if (lds_t) {
-            ti = trow_s[w];
-          } else {
-            const long long tg = trow[w];
-            ti = (tg != a.ignore_index && tg >= 0 && tg < Cm) ? (int)tg : -1;
-          }
+        hd_lerp_rows_pk<CT, SL>(L0, L1, lh, v0, dv);
+        for (int w = cl.w_lo; w < cl.w_hi; ++w) {
+          const Lerp lw = ac_lerp(w, tl.Wl, tl.W, tl.sw);
+          const int ti = tr.get(w);
           const bool valid = ti >= 0;
           const f32x2 w1 = {lw.l1, lw.l1};
           f32x2 e[CP];
@@ -204,95 +119,19 @@ __global__ __launch_bounds__(HD_T) void ce_head_kernel(CeHeadArgs a) {
             loss += (mx - lt + __builtin_amdgcn_logf(se)) * HD_LN2;  // v_log_f32: log2
             cnt += 1.f;
           }
-          // the four tap products as two packed pairs (v_pk_fma_f32: (00, 01) and (10, 11))
-          const f32x2 k0 = {lh.l0 * lw.l0, lh.l0 * lw.l1};
-          const f32x2 k1 = {lh.l1 * lw.l0, lh.l1 * lw.l1};
-          const f32x2 iv = {inv, inv};
-#pragma unroll
-          for (int p = 0; p < CP; ++p) {
-            const f32x2 oh = {(valid && 2 * p == ti) ? 1.f : 0.f, (valid && 2 * p + 1 == ti) ? 1.f : 0.f};
-            const f32x2 g = e[p] * iv - oh;
-            const f32x2 gx = {g.x, g.x}, gy = {g.y, g.y};
-            a0[2 * p] = __builtin_elementwise_fma(k0, gx, a0[2 * p]);
-            a1[2 * p] = __builtin_elementwise_fma(k1, gx, a1[2 * p]);
-            if (2 * p + 1 < CT) {
-              a0[2 * p + 1] = __builtin_elementwise_fma(k0, gy, a0[2 * p + 1]);
-              a1[2 * p + 1] = __builtin_elementwise_fma(k1, gy, a1[2 * p + 1]);
-            }
-          }
+          hd_tap_accum_pk<CT>(a0, a1, e, inv, HdNoWeight{}, ti, valid, lh, lw);
         }
       }
     }
-    float acc00[CT], acc01[CT], acc10[CT], acc11[CT];
-#pragma unroll
-    for (int c = 0; c < CT; ++c) {
-      acc00[c] = a0[c].x;
-      acc01[c] = a0[c].y;
-      acc10[c] = a1[c].x;
-      acc11[c] = a1[c].y;
-    }
-    if (active) {
-      if (t == Wl - 1) {  // i1(w) == i0(w) on the last column: both taps are column t
-#pragma unroll
-        for (int c = 0; c < CT; ++c) {
-          acc00[c] += acc01[c];
-          acc10[c] += acc11[c];
-          acc01[c] = acc11[c] = 0.f;
-        }
-      }
-      if (hl1 == hl) {  // last row: both row taps are row hl
-#pragma unroll
-        for (int c = 0; c < CT; ++c) {
-          acc00[c] += acc10[c];
-          acc01[c] += acc11[c];
-          acc10[c] = acc11[c] = 0.f;
-        }
-      }
-    }
-    // ---- hand the (*, t+1) shares to thread t+1 through LDS -------------------------------
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < CT; ++c) {
-      s_L[tid * SL + c] = acc01[c];
-      s_L[((HD_T + 1) + tid) * SL + c] = acc11[c];
-    }
-    __syncthreads();
-    if (active) {
-      float* o0 = g0 + (((size_t)n * Hl + hl) * Wl + t) * ldl;
-      float* o1 = g1 + (((size_t)n * Hl + hl + 1) * Wl + t) * ldl;
-#pragma unroll
-      for (int c = 0; c < CT; ++c) {
-        if (c < Cm) {
-          const float left0 = tid > 0 ? s_L[(tid - 1) * SL + c] : s_carry[c];
-          const float left1 = tid > 0 ? s_L[((HD_T + 1) + tid - 1) * SL + c] : s_carry[CT + c];
-          o0[c] = acc00[c] + left0;
-          if (hl1 != hl) o1[c] = acc10[c] + left1;
-        }
-      }
-    }
-    __syncthreads();
-    if (tid == HD_T - 1) {  // column cb + HD_T starts the next chunk
-#pragma unroll
-      for (int c = 0; c < CT; ++c) {
-        s_carry[c] = acc01[c];
-        s_carry[CT + c] = acc11[c];
-      }
-    }
+    hd_tile_epilogue<CT>(a0, a1, tl, cl, s_L, (HD_T + 1) * SL, SL, s_carry, a.g_raw, g1, ldl, Cm);
   }
-  s_r1[tid] = loss;
-  s_r2[tid] = cnt;
-  __syncthreads();
-  for (int off = HD_T / 2; off > 0; off >>= 1) {
-    if (tid < off) {
-      s_r1[tid] += s_r1[tid + off];
-      s_r2[tid] += s_r2[tid + off];
-    }
-    __syncthreads();
-  }
+  s_r[0][tid] = loss;
+  s_r[1][tid] = cnt;
+  hd_block_reduce<2, 0>(s_r, nullptr, tid);
   if (tid == 0) {
-    const size_t pi = (size_t)n * Hl + hl;
-    a.part[2 * pi] = s_r1[0];
-    a.part[2 * pi + 1] = s_r2[0];
+    const size_t pi = (size_t)tl.n * tl.Hl + tl.hl;
+    a.part[2 * pi] = s_r[0][0];
+    a.part[2 * pi + 1] = s_r[1][0];
   }
 }
 
@@ -312,6 +151,11 @@ __global__ __launch_bounds__(HD_T) void ce_head_kernel(CeHeadArgs a) {
 // The walk's exponent follows w * sw in real arithmetic where the weights use fl(w * sw): at most
 // a few fp32 ulps of W/Wl in lw.l1, i.e. ~1e-4 relative in a probability at |dv| ~ 3 -- well
 // inside one 16-bit rounding of the stored gradient (tests/test_gpu_literal.py).
+// Of head_tile.hpp this kernel shares the tile geometry only.  At C = 19 it sits at 256 VGPRs with
+// ~64 spilled, and each further shared piece moved it: the int64 target rows and the epilogue
+// change its scratch (HdTargetRows: +8 B; hd_tile_epilogue: 264 -> 188 B), and HeadCols plus
+// hd_block_reduce measured 1.5 - 3 us slower on the cfg3 step (profiles/head_refactor_time.txt).
+// So the column bounds, the int64 target rows, the epilogue and the reduce stay inline below.
 template <typename T, int CT>
 __global__ __launch_bounds__(HD_T, 2) void ce_head2_kernel(CeHeadArgs a) {
   constexpr int CP = (CT + 1) / 2;
@@ -324,22 +168,18 @@ __global__ __launch_bounds__(HD_T, 2) void ce_head2_kernel(CeHeadArgs a) {
   __shared__ float s_carry[2 * CT];
   __shared__ signed char s_t[2 * HD_TMAX];
   __shared__ float s_r1[HD_T], s_r2[HD_T];
-  const int tid = threadIdx.x;
-  const int hl = blockIdx.x, n = blockIdx.y;
-  const int Hl = a.Hl, Wl = a.Wl, H = a.H, W = a.W, ldl = a.ldl;
-  const float sh = ac_scale(Hl, H), sw = ac_scale(Wl, W);
-  const int h_lo = hd_first_ge(hl, Hl, H, sh), h_hi = hd_first_ge(hl + 1, Hl, H, sh);
-  const int hl1 = min(hl + 1, Hl - 1);
+  const HeadTile tl(a.Hl, a.Wl, a.H, a.W);
+  const int tid = tl.tid, hl = tl.hl, n = tl.n, hl1 = tl.hl1, h_lo = tl.h_lo, h_hi = tl.h_hi;
+  const int Hl = tl.Hl, Wl = tl.Wl, H = tl.H, W = tl.W, ldl = a.ldl;
+  const float sh = tl.sh, sw = tl.sw;
   const uint16_t* lg = (const uint16_t*)a.logits + (size_t)n * Hl * Wl * ldl;
   float* g0 = a.g_raw;                              // own-row plane
   float* g1 = a.g_raw + (size_t)a.N * Hl * Wl * ldl;  // spill plane (row hl+1)
   const long long* tgt = a.target + (size_t)n * H * W;
   float loss = 0.f, cnt = 0.f;
   stamp(a.stamps, 0);
-  if (tid < 2 * CT) s_carry[tid] = 0.f;
-  if (hl == 0) {  // nothing spills into row 0
-    for (int i = tid; i < Wl * ldl; i += HD_T) g1[(size_t)n * Hl * Wl * ldl + i] = 0.f;
-  }
+  hd_carry_zero<CT>(s_carry, tid);
+  tl.zero_spill_row0(g1, ldl);
   // int8 targets (a.tgt8): 8 bytes per thread and row, HD_PD rows in flight (register ring)
   const bool t8 = a.tgt8 != nullptr && W <= HD_TMAX && W % 8 == 0;
   const bool t8own = tid * 8 < W;
@@ -386,7 +226,7 @@ __global__ __launch_bounds__(HD_T, 2) void ce_head2_kernel(CeHeadArgs a) {
     if (cb == 0) stamp(a.stamps, 1);
     const int t = cb + tid;
     const bool active = t < Wl;
-    f32x2 a0[CT], a1[CT];  // (acc00, acc01) own row, columns t / t+1; (acc10, acc11) row hl+1
+    f32x2 a0[CT], a1[CT];
 #pragma unroll
     for (int c = 0; c < CT; ++c) a0[c] = a1[c] = f32x2{0.f, 0.f};
     const int w_lo = active ? hd_first_ge(t, Wl, W, sw) : 0;
@@ -394,7 +234,6 @@ __global__ __launch_bounds__(HD_T, 2) void ce_head2_kernel(CeHeadArgs a) {
     const bool lds_t = W <= HD_TMAX;
     constexpr int TPT = HD_TMAX / HD_T;
     int tnext[TPT];
-
     auto load_trow = [&](int h) {
       const long long* tr = tgt + (size_t)h * W;
 #pragma unroll
@@ -546,6 +385,7 @@ __global__ __launch_bounds__(HD_T, 2) void ce_head2_kernel(CeHeadArgs a) {
       }
     }
     if (cb == 0) stamp(a.stamps, 2);
+    // hd_tile_epilogue<CT>, inline (above), with the hand-off through s_oh as [2][HD_T][CT] floats
     float acc00[CT], acc01[CT], acc10[CT], acc11[CT];
 #pragma unroll
     for (int c = 0; c < CT; ++c) {
@@ -555,7 +395,7 @@ __global__ __launch_bounds__(HD_T, 2) void ce_head2_kernel(CeHeadArgs a) {
       acc11[c] = a1[c].y;
     }
     if (active) {
-      if (t == Wl - 1) {  // i1(w) == i0(w) on the last column: both taps are column t
+      if (t == Wl - 1) {
 #pragma unroll
         for (int c = 0; c < CT; ++c) {
           acc00[c] += acc01[c];
@@ -563,7 +403,7 @@ __global__ __launch_bounds__(HD_T, 2) void ce_head2_kernel(CeHeadArgs a) {
           acc01[c] = acc11[c] = 0.f;
         }
       }
-      if (hl1 == hl) {  // last row: both row taps are row hl
+      if (hl1 == hl) {
 #pragma unroll
         for (int c = 0; c < CT; ++c) {
           acc00[c] += acc10[c];
@@ -572,7 +412,6 @@ __global__ __launch_bounds__(HD_T, 2) void ce_head2_kernel(CeHeadArgs a) {
         }
       }
     }
-    // ---- hand the (*, t+1) shares to thread t+1 through LDS (s_oh as [2][HD_T][CT] floats) ---
     float* s_h = reinterpret_cast<float*>(s_oh);
     __syncthreads();
 #pragma unroll
@@ -593,7 +432,7 @@ __global__ __launch_bounds__(HD_T, 2) void ce_head2_kernel(CeHeadArgs a) {
       }
     }
     __syncthreads();
-    if (tid == HD_T - 1) {  // column cb + HD_T starts the next chunk
+    if (tid == HD_T - 1) {
 #pragma unroll
       for (int c = 0; c < CT; ++c) {
         s_carry[c] = acc01[c];
@@ -661,7 +500,45 @@ int ce_pack_targets(const long long* t, long long n, int C, long long ignore_ind
 
 int ce_head_parts(int N, int Hl, int Wl) { return N * Hl; }
 
-__global__ __launch_bounds__(256) void ce_head_finalize_kernel(const float* part, int P, float* out) {
+// ---- instance selection ------------------------------------------------------------------------
+// Every head is instantiated for the plan dtypes x the class counts (19, exact), (2, exact) and
+// the generic (8, C <= 8) and (HD_CMAX, C <= HD_CMAX); f is called with the one HdInst that
+// serves (C, dtype).  A head without some instance (Dice: the two-class form is its own MODE)
+// leaves it out with `if constexpr` in f.
+template <typename T_, int CT_, bool EXACT_>
+struct HdInst {
+  using T = T_;
+  static constexpr int CT = CT_;
+  static constexpr bool EXACT = EXACT_;
+};
+template <typename T_>
+struct HdType {
+  using T = T_;
+};
+template <class F>
+static void hd_dispatch_dtype(int dtype, F f) {
+  if (dtype == DT_F32) f(HdType<float>{});
+  else if (dtype == DT_F16) f(HdType<f16>{});
+  else f(HdType<bf16>{});
+}
+template <class F>
+static void hd_dispatch(int C, int dtype, F f) {
+  hd_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::T;
+    if (C == 19) f(HdInst<T, 19, true>{});
+    else if (C == 2) f(HdInst<T, 2, true>{});
+    else if (C <= 8) f(HdInst<T, 8, false>{});
+    else f(HdInst<T, HD_CMAX, false>{});
+  });
+}
+
+// partials [P][2] -> out2 = (sum / count, count): the mean loss (NaN without a valid pixel) and
+// its denominator, in fp64 and a fixed order.  The OHEM head's sums are weighted, and with thr
+// given (its pass 2) nothing is written when *thr is bit-equal to thresh: pass 1's result stands.
+__global__ __launch_bounds__(256) void ce_head_finalize_kernel(const float* part, int P,
+                                                               const float* thr, float thresh,
+                                                               float* out) {
+  if (thr && __float_as_uint(*thr) == __float_as_uint(thresh)) return;
   __shared__ double r1[256], r2[256];
   double s1 = 0.0, s2 = 0.0;
   for (int p = threadIdx.x; p < P; p += 256) {
@@ -701,40 +578,27 @@ int ce_head(const CeHeadArgs& a, float* out2, int dtype, hipStream_t st) {
     ProfScope ps(PK_CE, st, (dtype == DT_F32 ? 4.0 : 2.0) * a.N * a.Hl * a.Wl * a.C +
                                 8.0 * a.N * a.H * a.W + 2.0 * 4.0 * a.N * a.Hl * a.Wl * a.C,
                  0.0);
-    const bool f32 = dtype == DT_F32;
     // (16-bit plans: the walked-exponential kernel; round 3's one-hot-select kernel for these
     // shapes measured 211 vs 158-164 us and was retired as a switch in r05)
     if (ce_head2_form(a.C, a.ldl, dtype)) {
       CeHeadArgs as = a;
       as.stamps = stamp_region();
-      if (a.C == 19) {
-        if (dtype == DT_F16) prof_launch(ce_head2_kernel<f16, 19>, grid, HD_T, 0, st, as);
-        else prof_launch(ce_head2_kernel<bf16, 19>, grid, HD_T, 0, st, as);
-      } else {
-        if (dtype == DT_F16) prof_launch(ce_head2_kernel<f16, 2>, grid, HD_T, 0, st, as);
-        else prof_launch(ce_head2_kernel<bf16, 2>, grid, HD_T, 0, st, as);
-      }
-    } else if (a.C == 19) {
-      if (f32) prof_launch(ce_head_kernel<float, 19, true>, grid, HD_T, 0, st, a);
-      else if (dtype == DT_F16) prof_launch(ce_head_kernel<f16, 19, true>, grid, HD_T, 0, st, a);
-      else prof_launch(ce_head_kernel<bf16, 19, true>, grid, HD_T, 0, st, a);
-    } else if (a.C == 2) {
-      if (f32) prof_launch(ce_head_kernel<float, 2, true>, grid, HD_T, 0, st, a);
-      else if (dtype == DT_F16) prof_launch(ce_head_kernel<f16, 2, true>, grid, HD_T, 0, st, a);
-      else prof_launch(ce_head_kernel<bf16, 2, true>, grid, HD_T, 0, st, a);
-    } else if (a.C <= 8) {
-      if (f32) prof_launch(ce_head_kernel<float, 8, false>, grid, HD_T, 0, st, a);
-      else if (dtype == DT_F16) prof_launch(ce_head_kernel<f16, 8, false>, grid, HD_T, 0, st, a);
-      else prof_launch(ce_head_kernel<bf16, 8, false>, grid, HD_T, 0, st, a);
+      hd_dispatch(a.C, dtype, [&](auto i) {
+        using I = decltype(i);
+        if constexpr (I::EXACT && !std::is_same<typename I::T, float>::value)
+          prof_launch((ce_head2_kernel<typename I::T, I::CT>), grid, HD_T, 0, st, as);
+      });
     } else {
-      if (f32) prof_launch(ce_head_kernel<float, HD_CMAX, false>, grid, HD_T, 0, st, a);
-      else if (dtype == DT_F16) prof_launch(ce_head_kernel<f16, HD_CMAX, false>, grid, HD_T, 0, st, a);
-      else prof_launch(ce_head_kernel<bf16, HD_CMAX, false>, grid, HD_T, 0, st, a);
+      hd_dispatch(a.C, dtype, [&](auto i) {
+        using I = decltype(i);
+        prof_launch((ce_head_kernel<typename I::T, I::CT, I::EXACT>), grid, HD_T, 0, st, a);
+      });
     }
     int rc = check_launch("ce_head");
     if (rc) return rc;
   }
-  prof_launch(ce_head_finalize_kernel, 1, 256, 0, st, a.part, ce_head_parts(a.N, a.Hl, a.Wl), out2);
+  prof_launch(ce_head_finalize_kernel, 1, 256, 0, st, a.part, ce_head_parts(a.N, a.Hl, a.Wl),
+              (const float*)nullptr, 0.f, out2);
   return check_launch("ce_head_finalize");
 }
 
@@ -753,12 +617,11 @@ __global__ __launch_bounds__(256) void ce_head_scale_kernel(const float* g_raw, 
 int ce_head_scale(const float* g_raw, void* g, long long M, int C, int ld, const float* gout,
                   const float* out2, int dtype, hipStream_t st, float weight) {
   const int total = (int)(M * ld);
-  if (dtype == DT_F32)
-    prof_launch(ce_head_scale_kernel<float>, cdiv(total, 256), 256, 0, st, g_raw, (float*)g, (int)M, C, ld, gout, out2, weight);
-  else if (dtype == DT_F16)
-    prof_launch(ce_head_scale_kernel<f16>, cdiv(total, 256), 256, 0, st, g_raw, (f16*)g, (int)M, C, ld, gout, out2, weight);
-  else
-    prof_launch(ce_head_scale_kernel<bf16>, cdiv(total, 256), 256, 0, st, g_raw, (bf16*)g, (int)M, C, ld, gout, out2, weight);
+  hd_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::T;
+    prof_launch(ce_head_scale_kernel<T>, cdiv(total, 256), 256, 0, st, g_raw, (T*)g, (int)M, C, ld,
+                gout, out2, weight);
+  });
   return check_launch("ce_head_scale");
 }
 
@@ -780,10 +643,8 @@ int aux_loss_combine(const float* main, const float* aux, float aux_weight, floa
 }
 
 // ---- Dice / Focal+Dice head (utils/loss.py:12-100) -------------------------------------------
-// The same work layout as ce_head_kernel (workgroup = (low-res row, image), thread = low-res
-// column, two logit rows in LDS, every full-resolution pixel once, neighbour shares added in a
-// fixed order).  Per pixel p = softmax(z), p1 = p[1], t = float(target) (targets outside [0, C)
-// count as 0):
+// The work layout of head_tile.hpp.  Per pixel p = softmax(z), p1 = p[1], t = float(target)
+// (targets outside [0, C) count as 0):
 //   sums      I = sum p1 t, S = sum p1, T = sum t, F = sum alpha (1 - pt)^gamma ce
 //   loss      wd (1 - (2 I + s) / U) + wf F / npix,  U = S + T + s
 //   gradient  dz_c = (a t + b) p1 ([c == 1] - p_c) + f dfocal/dce (p_c - [c == t]),
@@ -826,102 +687,41 @@ __global__ __launch_bounds__(HD_T) void dice_head_kernel(DiceHeadArgs a) {
   __shared__ float s_carry[2 * NA];
   __shared__ __attribute__((aligned(8))) signed char s_t[2 * HD_TMAX];
   __shared__ float s_r[4][HD_T];
-  const int tid = threadIdx.x;
-  const int hl = blockIdx.x, n = blockIdx.y;
-  const int Hl = a.Hl, Wl = a.Wl, H = a.H, W = a.W, ldl = a.ldl, gld = a.gld;
+  const HeadTile tl(a.Hl, a.Wl, a.H, a.W);
+  const int tid = tl.tid, ldl = a.ldl, gld = a.gld;
   const int Cm = EXACT ? CT : a.C;
-  const float sh = ac_scale(Hl, H), sw = ac_scale(Wl, W);
-  const int h_lo = hd_first_ge(hl, Hl, H, sh), h_hi = hd_first_ge(hl + 1, Hl, H, sh);
-  const int hl1 = min(hl + 1, Hl - 1);
-  const T* lg = (const T*)a.logits + (size_t)n * Hl * Wl * ldl;
-  float* g0 = a.planes;                                // own-row plane
-  float* g1 = a.planes + (size_t)a.N * Hl * Wl * gld;  // spill plane (row hl+1)
-  const long long* tgt = a.target + (size_t)n * H * W;
+  const T* lg = (const T*)a.logits + tl.image(ldl);
+  float* g1 = tl.spill_plane(a.planes, a.N, gld);
   const bool focal = a.focal != 0;
   DiceCoef kf{0.f, 0.f, 0.f};
-  if (MODE == 2) kf = dice_coef(a.stats, a.smooth, a.wd, a.wf, (double)a.N * H * W);
+  if (MODE == 2) kf = dice_coef(a.stats, a.smooth, a.wd, a.wf, (double)a.N * tl.H * tl.W);
   float sI = 0.f, sS = 0.f, sT = 0.f, sF = 0.f;
-  if (tid < 2 * NA) s_carry[tid] = 0.f;
-  if (MODE != 1 && hl == 0) {  // nothing spills into row 0
-    for (int i = tid; i < Wl * gld; i += HD_T) g1[(size_t)n * Hl * Wl * gld + i] = 0.f;
-  }
-  // targets: one full-resolution row at a time in LDS as int8 (the next row's loads in flight
-  // during the current row), from the plan's packed int8 copy (8 per thread) or the int64 rows;
-  // rows wider than HD_TMAX are read per pixel
-  const bool lds_t = W <= HD_TMAX;
-  const bool t8 = a.tgt8 != nullptr && lds_t && W % 8 == 0;
-  const bool t8own = tid * 8 < W;
-  const signed char* trow8 = a.tgt8 + (size_t)n * H * W + tid * 8;
-  constexpr int TPT = HD_TMAX / HD_T;
-  for (int cb = 0; cb < Wl; cb += HD_T) {
-    __syncthreads();
-    for (int i = tid; i < 2 * (HD_T + 1) * CT; i += HD_T) {
-      const int c = i % CT, jr = i / CT;
-      const int j = jr % (HD_T + 1), r = jr / (HD_T + 1);
-      const int col = min(cb + j, Wl - 1);
-      const int row = r ? hl1 : hl;
-      // staged in log2 units: the softmax runs on v_exp_f32 (2^x)
-      s_L[(r * (HD_T + 1) + j) * SL + c] =
-          c < Cm ? ld1(lg + ((size_t)row * Wl + col) * ldl + c) * HD_LOG2E : 0.f;
-    }
-    __syncthreads();
-    const int t = cb + tid;
-    const bool active = t < Wl;
-    f32x2 a0[NA], a1[NA];  // (acc00, acc01) own row, columns t / t+1; (acc10, acc11) row hl+1
+  hd_carry_zero<NA>(s_carry, tid);
+  if (MODE != 1) tl.zero_spill_row0(g1, gld);
+  for (int cb = 0; cb < tl.Wl; cb += HD_T) {
+    hd_stage_rows_f32<T, CT, SL>(s_L, lg, tl, cb, Cm, ldl);
+    const HeadCols cl(tl, cb);
+    f32x2 a0[NA], a1[NA];
 #pragma unroll
     for (int c = 0; c < NA; ++c) a0[c] = a1[c] = f32x2{0.f, 0.f};
-    const int w_lo = active ? hd_first_ge(t, Wl, W, sw) : 0;
-    const int w_hi = active ? hd_first_ge(t + 1, Wl, W, sw) : 0;
-    int tnext[TPT];
-    uint2 tq = make_uint2(0u, 0u);
-    auto load_trow = [&](int h) {
-      if (t8) {
-        if (t8own) tq = *reinterpret_cast<const uint2*>(trow8 + (size_t)h * W);
-        return;
-      }
-      const long long* tr = tgt + (size_t)h * W;
-#pragma unroll
-      for (int k = 0; k < TPT; ++k) {
-        const int w = tid + HD_T * k;
-        const long long tg = tr[w < W ? w : 0];
-        tnext[k] = (w < W && tg >= 0 && tg < Cm) ? (int)tg : 0;
-      }
-    };
-    if (lds_t && h_lo < h_hi) load_trow(h_lo);
+    HdTargetRows<HdClampZero, true> tr(tl, a.target, a.tgt8, s_t, HdClampZero{}, Cm,
+                                       tl.W <= HD_TMAX);
+    tr.start(tl.h_lo, tl.h_hi);
     const float* L0 = &s_L[tid * SL];
     const float* L1 = &s_L[((HD_T + 1) + tid) * SL];
-    for (int h = h_lo; h < h_hi; ++h) {
-      signed char* trow_s = s_t + (h & 1) * HD_TMAX;
-      if (lds_t) {
-        if (t8) {
-          if (t8own) *reinterpret_cast<uint2*>(trow_s + tid * 8) = tq;
-        } else {
-#pragma unroll
-          for (int k = 0; k < TPT; ++k)
-            if (tid + HD_T * k < W) trow_s[tid + HD_T * k] = (signed char)tnext[k];
-        }
-        __syncthreads();
-        if (h + 1 < h_hi) load_trow(h + 1);
-      }
-      if (active) {
-        const Lerp lh = ac_lerp(h, Hl, H, sh);
+    for (int h = tl.h_lo; h < tl.h_hi; ++h) {
+      tr.commit(h, tl.h_hi);
+      if (cl.active) {
+        const Lerp lh = ac_lerp(h, tl.Hl, tl.H, tl.sh);
         float v0[CT], dv[CT];  // row-interpolated logits of column t, and (column t+1) - v0
 #pragma unroll
         for (int c = 0; c < CT; ++c) {
           v0[c] = fmaf(lh.l1, L1[c], lh.l0 * L0[c]);
           dv[c] = fmaf(lh.l1, L1[SL + c], lh.l0 * L0[SL + c]) - v0[c];
         }
-        const long long* trow = tgt + (size_t)h * W;
-        for (int w = w_lo; w < w_hi; ++w) {
-          const Lerp lw = ac_lerp(w, Wl, W, sw);
-          int ti;
-          if (lds_t) {
-            ti = trow_s[w];
-            ti = ti < 0 ? 0 : ti;  // packed: -1 = outside [0, C)
-          } else {
-            const long long tg = trow[w];
-            ti = (tg >= 0 && tg < Cm) ? (int)tg : 0;
-          }
+        for (int w = cl.w_lo; w < cl.w_hi; ++w) {
+          const Lerp lw = ac_lerp(w, tl.Wl, tl.W, tl.sw);
+          const int ti = tr.get(w);
           const float tf = (float)ti;
           float e[CT];
           float mx = -INFINITY;
@@ -982,77 +782,16 @@ __global__ __launch_bounds__(HD_T) void dice_head_kernel(DiceHeadArgs a) {
       }
     }
     if (MODE == 1) continue;  // the sums pass writes no plane (uniform: no barrier is skipped)
-    float acc00[NA], acc01[NA], acc10[NA], acc11[NA];
-#pragma unroll
-    for (int c = 0; c < NA; ++c) {
-      acc00[c] = a0[c].x;
-      acc01[c] = a0[c].y;
-      acc10[c] = a1[c].x;
-      acc11[c] = a1[c].y;
-    }
-    if (active) {
-      if (t == Wl - 1) {  // i1(w) == i0(w) on the last column: both taps are column t
-#pragma unroll
-        for (int c = 0; c < NA; ++c) {
-          acc00[c] += acc01[c];
-          acc10[c] += acc11[c];
-          acc01[c] = acc11[c] = 0.f;
-        }
-      }
-      if (hl1 == hl) {  // last row: both row taps are row hl
-#pragma unroll
-        for (int c = 0; c < NA; ++c) {
-          acc00[c] += acc10[c];
-          acc01[c] += acc11[c];
-          acc10[c] = acc11[c] = 0.f;
-        }
-      }
-    }
-    // ---- hand the (*, t+1) shares to thread t+1 through LDS -------------------------------
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < NA; ++c) {
-      s_L[tid * SL + c] = acc01[c];
-      s_L[((HD_T + 1) + tid) * SL + c] = acc11[c];
-    }
-    __syncthreads();
-    if (active) {
-      float* o0 = g0 + (((size_t)n * Hl + hl) * Wl + t) * gld;
-      float* o1 = g1 + (((size_t)n * Hl + hl + 1) * Wl + t) * gld;
-      const int nw = MODE == 0 ? 3 : Cm;
-#pragma unroll
-      for (int c = 0; c < NA; ++c) {
-        if (c < nw) {
-          const float left0 = tid > 0 ? s_L[(tid - 1) * SL + c] : s_carry[c];
-          const float left1 = tid > 0 ? s_L[((HD_T + 1) + tid - 1) * SL + c] : s_carry[NA + c];
-          o0[c] = acc00[c] + left0;
-          if (hl1 != hl) o1[c] = acc10[c] + left1;
-        }
-      }
-    }
-    __syncthreads();
-    if (tid == HD_T - 1) {  // column cb + HD_T starts the next chunk
-#pragma unroll
-      for (int c = 0; c < NA; ++c) {
-        s_carry[c] = acc01[c];
-        s_carry[NA + c] = acc11[c];
-      }
-    }
+    hd_tile_epilogue<NA>(a0, a1, tl, cl, s_L, (HD_T + 1) * SL, SL, s_carry, a.planes, g1, gld,
+                         MODE == 0 ? 3 : Cm);
   }
   if (MODE == 2) return;
   s_r[0][tid] = sI;
   s_r[1][tid] = sS;
   s_r[2][tid] = sT;
   s_r[3][tid] = sF;
-  __syncthreads();
-  for (int off = HD_T / 2; off > 0; off >>= 1) {
-    if (tid < off) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) s_r[k][tid] += s_r[k][tid + off];
-    }
-    __syncthreads();
-  }
-  if (tid < 4) a.part[4 * ((size_t)n * Hl + hl) + tid] = s_r[tid][0];
+  hd_block_reduce<4, 0>(s_r, nullptr, tid);
+  if (tid < 4) a.part[4 * ((size_t)tl.n * tl.Hl + tl.hl) + tid] = s_r[tid][0];
 }
 
 // partials [P][4] -> stats (I, S, T, F) in fp64, fixed order, and the loss
@@ -1090,21 +829,14 @@ long long dice_head_ws_bytes(int N, int Hl, int Wl, int C, int ldl) {
   return (planes + 255) / 256 * 256 + part;
 }
 
-template <typename T, int CT, bool EXACT, int MODE>
-static void dice_head_launch(const DiceHeadArgs& a, dim3 grid, hipStream_t st) {
-  prof_launch((dice_head_kernel<T, CT, EXACT, MODE>), grid, HD_T, 0, st, a);
-}
-template <int CT, bool EXACT, int MODE>
-static void dice_head_launch_dt(const DiceHeadArgs& a, int dtype, dim3 grid, hipStream_t st) {
-  if (dtype == DT_F32) dice_head_launch<float, CT, EXACT, MODE>(a, grid, st);
-  else if (dtype == DT_F16) dice_head_launch<f16, CT, EXACT, MODE>(a, grid, st);
-  else dice_head_launch<bf16, CT, EXACT, MODE>(a, grid, st);
-}
+// MODE 0 is the <2, true> instance and only that; MODE 1 / 2 have no <2, true>
 template <int MODE>
-static void dice_head_launch_c(const DiceHeadArgs& a, int dtype, dim3 grid, hipStream_t st) {
-  if (a.C == 19) dice_head_launch_dt<19, true, MODE>(a, dtype, grid, st);
-  else if (a.C <= 8) dice_head_launch_dt<8, false, MODE>(a, dtype, grid, st);
-  else dice_head_launch_dt<HD_CMAX, false, MODE>(a, dtype, grid, st);
+static void dice_head_launch(const DiceHeadArgs& a, int dtype, dim3 grid, hipStream_t st) {
+  hd_dispatch(a.C, dtype, [&](auto i) {
+    using I = decltype(i);
+    if constexpr ((I::CT == 2) == (MODE == 0))
+      prof_launch((dice_head_kernel<typename I::T, I::CT, I::EXACT, MODE>), grid, HD_T, 0, st, a);
+  });
 }
 
 int dice_head(const DiceHeadArgs& a0, void* head_ws, float* loss, double* stats, int dtype,
@@ -1125,19 +857,19 @@ int dice_head(const DiceHeadArgs& a0, void* head_ws, float* loss, double* stats,
   const double lb = (dtype == DT_F32 ? 4.0 : 2.0) * M * a.C, tb = (a.tgt8 ? 1.0 : 8.0) * npix;
   if (a.C == 2) {
     ProfScope ps(PK_CE, st, lb + tb + 2.0 * 4.0 * M * 3, 0.0);
-    dice_head_launch_dt<2, true, 0>(a, dtype, grid, st);
+    dice_head_launch<0>(a, dtype, grid, st);
     if (int rc = check_launch("dice_head")) return rc;
     prof_launch(dice_head_finalize_kernel, 1, 256, 0, st, a.part, P, a.smooth, a.wd, a.wf, npix,
                 stats, loss);
     return check_launch("dice_head_finalize");
   }
   ProfScope ps(PK_CE, st, 2.0 * (lb + tb) + 2.0 * 4.0 * M * a.C, 0.0);
-  dice_head_launch_c<1>(a, dtype, grid, st);
+  dice_head_launch<1>(a, dtype, grid, st);
   if (int rc = check_launch("dice_head (sums)")) return rc;
   prof_launch(dice_head_finalize_kernel, 1, 256, 0, st, a.part, P, a.smooth, a.wd, a.wf, npix,
               stats, loss);
   if (int rc = check_launch("dice_head_finalize")) return rc;
-  dice_head_launch_c<2>(a, dtype, grid, st);
+  dice_head_launch<2>(a, dtype, grid, st);
   return check_launch("dice_head (gradient)");
 }
 
@@ -1175,21 +907,18 @@ int dice_head_scale(const void* head_ws, void* g, long long M, int C, int ld, co
                     hipStream_t st, float weight) {
   const int total = (int)(M * ld);
   const float* pl = (const float*)head_ws;
-  if (dtype == DT_F32)
-    prof_launch(dice_head_scale_kernel<float>, cdiv(total, 256), 256, 0, st, pl, (float*)g, (int)M, C, ld, gout, stats, smooth, wd, wf, npix, weight);
-  else if (dtype == DT_F16)
-    prof_launch(dice_head_scale_kernel<f16>, cdiv(total, 256), 256, 0, st, pl, (f16*)g, (int)M, C, ld, gout, stats, smooth, wd, wf, npix, weight);
-  else
-    prof_launch(dice_head_scale_kernel<bf16>, cdiv(total, 256), 256, 0, st, pl, (bf16*)g, (int)M, C, ld, gout, stats, smooth, wd, wf, npix, weight);
+  hd_dispatch_dtype(dtype, [&](auto t) {
+    using T = typename decltype(t)::T;
+    prof_launch(dice_head_scale_kernel<T>, cdiv(total, 256), 256, 0, st, pl, (T*)g, (int)M, C, ld,
+                gout, stats, smooth, wd, wf, npix, weight);
+  });
   return check_launch("dice_head_scale");
 }
 
 // ---- OHEM head (utils/loss.py:127-206, the criterion of train.py:189-191) ----------------------
 // nn.CrossEntropyLoss(weight, ignore_index) over the KEPT pixels of the upsampled logits, a pixel
 // being kept when it is labelled and the softmax probability of its label is <= the threshold of
-// utils/loss.py:159-170.  The same work layout as ce_head_kernel (workgroup = (low-res row,
-// image), thread = low-res column, two logit rows in LDS, every full-resolution pixel once,
-// neighbour shares and the row spill added in a fixed order).  Probabilities are evaluated per
+// utils/loss.py:159-170.  The work layout of head_tile.hpp.  Probabilities are evaluated per
 // pixel (v_exp_f32 / v_rcp_f32) for every plan dtype, so one error bound holds for all of them.
 //   PASS 1: prob[pixel] = p_label (2.0: ignored / out of range) as an fp32 plane, the two integer
 //     counters ohem_threshold_dev reads (#labelled, #(prob <= thresh)), and -- assuming the
@@ -1214,112 +943,43 @@ __global__ __launch_bounds__(HD_T) void ohem_head_kernel(OhemHeadArgs a) {
   __shared__ float s_carry[2 * CT];
   __shared__ float s_w[CT];
   __shared__ __attribute__((aligned(8))) signed char s_t[2 * HD_TMAX];
-  __shared__ float s_r1[HD_T], s_r2[HD_T];
-  __shared__ unsigned s_c1[HD_T], s_c2[HD_T];
-  const int tid = threadIdx.x;
-  const int hl = blockIdx.x, n = blockIdx.y;
-  const int Hl = a.Hl, Wl = a.Wl, H = a.H, W = a.W, ldl = a.ldl;
+  __shared__ float s_r[2][HD_T];
+  __shared__ unsigned s_c[2][HD_T];
+  const HeadTile tl(a.Hl, a.Wl, a.H, a.W);
+  const int tid = tl.tid, ldl = a.ldl;
   const int Cm = EXACT ? CT : a.C;
-  const float sh = ac_scale(Hl, H), sw = ac_scale(Wl, W);
-  const int h_lo = hd_first_ge(hl, Hl, H, sh), h_hi = hd_first_ge(hl + 1, Hl, H, sh);
-  const int hl1 = min(hl + 1, Hl - 1);
-  const T* lg = (const T*)a.logits + (size_t)n * Hl * Wl * ldl;
-  float* g0 = a.g_raw;                              // own-row plane
-  float* g1 = a.g_raw + (size_t)a.N * Hl * Wl * ldl;  // spill plane (row hl+1)
-  const long long* tgt = a.target + (size_t)n * H * W;
-  float* prob = a.prob + (size_t)n * H * W;
+  const T* lg = (const T*)a.logits + tl.image(ldl);
+  float* g1 = tl.spill_plane(a.g_raw, a.N, ldl);
+  float* prob = a.prob + (size_t)tl.n * tl.H * tl.W;
   float loss = 0.f, wsum = 0.f;
   unsigned nlab = 0u, nle = 0u;
-  if (tid < 2 * CT) s_carry[tid] = 0.f;
+  hd_carry_zero<CT>(s_carry, tid);
   if (tid < CT) s_w[tid] = (a.weight && tid < Cm) ? a.weight[tid] : 1.f;
-  if (hl == 0) {  // nothing spills into row 0
-    for (int i = tid; i < Wl * ldl; i += HD_T) g1[(size_t)n * Hl * Wl * ldl + i] = 0.f;
-  }
-  // PASS 1 targets: one full-resolution row at a time in LDS as int8 (the next row's loads in
-  // flight during the current row), from the plan's packed int8 copy (8 per thread) or the int64
-  // rows; rows wider than HD_TMAX are read per pixel.  PASS 2 reads the targets of kept pixels only.
-  const bool lds_t = PASS == 1 && W <= HD_TMAX;
-  const bool t8 = a.tgt8 != nullptr && W <= HD_TMAX && W % 8 == 0;
-  const bool t8own = tid * 8 < W;
-  const signed char* tgt8 = a.tgt8 + (size_t)n * H * W;
-  constexpr int TPT = HD_TMAX / HD_T;
-  for (int cb = 0; cb < Wl; cb += HD_T) {
-    __syncthreads();
-    for (int i = tid; i < 2 * (HD_T + 1) * CT; i += HD_T) {
-      const int c = i % CT, jr = i / CT;
-      const int j = jr % (HD_T + 1), r = jr / (HD_T + 1);
-      const int col = min(cb + j, Wl - 1);
-      const int row = r ? hl1 : hl;
-      // staged in log2 units: the softmax runs on v_exp_f32 (2^x)
-      s_L[(r * (HD_T + 1) + j) * SL + c] =
-          c < Cm ? ld1(lg + ((size_t)row * Wl + col) * ldl + c) * HD_LOG2E : 0.f;
-    }
-    __syncthreads();
-    const int t = cb + tid;
-    const bool active = t < Wl;
-    f32x2 a0[CT], a1[CT];  // (acc00, acc01) own row, columns t / t+1; (acc10, acc11) row hl+1
+  tl.zero_spill_row0(g1, ldl);
+  for (int cb = 0; cb < tl.Wl; cb += HD_T) {
+    hd_stage_rows_f32<T, CT, SL>(s_L, lg, tl, cb, Cm, ldl);
+    const HeadCols cl(tl, cb);
+    f32x2 a0[CT], a1[CT];
 #pragma unroll
     for (int c = 0; c < CT; ++c) a0[c] = a1[c] = f32x2{0.f, 0.f};
-    const int w_lo = active ? hd_first_ge(t, Wl, W, sw) : 0;
-    const int w_hi = active ? hd_first_ge(t + 1, Wl, W, sw) : 0;
-    int tnext[TPT];
-    uint2 tq = make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);
-    auto load_trow = [&](int h) {
-      if (t8) {
-        if (t8own) tq = *reinterpret_cast<const uint2*>(tgt8 + (size_t)h * W + tid * 8);
-        return;
-      }
-      const long long* tr = tgt + (size_t)h * W;
-#pragma unroll
-      for (int k = 0; k < TPT; ++k) {
-        const int w = tid + HD_T * k;
-        const long long tg = tr[w < W ? w : 0];
-        tnext[k] = (w < W && tg != a.ignore_index && tg >= 0 && tg < Cm) ? (int)tg : -1;
-      }
-    };
-    if (lds_t && h_lo < h_hi) load_trow(h_lo);
+    // PASS 1 stages the target rows; PASS 2 reads the targets of kept pixels only
+    HdTargetRows<HdIgnoreAware, true> tr(tl, a.target, a.tgt8, s_t, HdIgnoreAware{a.ignore_index},
+                                         Cm, PASS == 1 && tl.W <= HD_TMAX);
+    tr.start(tl.h_lo, tl.h_hi);
     const float* L0 = &s_L[tid * SL];
     const float* L1 = &s_L[((HD_T + 1) + tid) * SL];
-    for (int h = h_lo; h < h_hi; ++h) {
-      signed char* trow_s = s_t + (h & 1) * HD_TMAX;
-      if (lds_t) {  // (uniform: every thread of the workgroup takes the barrier)
-        if (t8) {
-          if (t8own) *reinterpret_cast<uint2*>(trow_s + tid * 8) = tq;
-        } else {
-#pragma unroll
-          for (int k = 0; k < TPT; ++k)
-            if (tid + HD_T * k < W) trow_s[tid + HD_T * k] = (signed char)tnext[k];
-        }
-        __syncthreads();
-        if (h + 1 < h_hi) load_trow(h + 1);
-      }
-      if (active) {
-        const Lerp lh = ac_lerp(h, Hl, H, sh);
-        // class pairs: v0 = the row-interpolated logits of column t, dv = (column t+1) - v0
+    for (int h = tl.h_lo; h < tl.h_hi; ++h) {
+      tr.commit(h, tl.h_hi);
+      if (cl.active) {
+        const Lerp lh = ac_lerp(h, tl.Hl, tl.H, tl.sh);
         f32x2 v0[CP], dv[CP];
-        const f32x2 h0 = {lh.l0, lh.l0}, h1 = {lh.l1, lh.l1};
-#pragma unroll
-        for (int p = 0; p < CP; ++p) {
-          const int c = 2 * p, c1 = c + 1 < CT ? c + 1 : c;
-          const f32x2 l00 = {L0[c], c + 1 < CT ? L0[c1] : 0.f};
-          const f32x2 l10 = {L1[c], c + 1 < CT ? L1[c1] : 0.f};
-          const f32x2 l01 = {L0[SL + c], c + 1 < CT ? L0[SL + c1] : 0.f};
-          const f32x2 l11 = {L1[SL + c], c + 1 < CT ? L1[SL + c1] : 0.f};
-          v0[p] = __builtin_elementwise_fma(h1, l10, h0 * l00);
-          dv[p] = __builtin_elementwise_fma(h1, l11, h0 * l01) - v0[p];
-        }
-        const long long* trow = tgt + (size_t)h * W;
-        float* prow = prob + (size_t)h * W;
-        for (int w = w_lo; w < w_hi; ++w) {
+        hd_lerp_rows_pk<CT, SL>(L0, L1, lh, v0, dv);
+        float* prow = prob + (size_t)h * tl.W;
+        for (int w = cl.w_lo; w < cl.w_hi; ++w) {
           int ti;
           float pv = 2.f;
           if (PASS == 1) {
-            if (lds_t) {
-              ti = trow_s[w];
-            } else {
-              const long long tg = trow[w];
-              ti = (tg != a.ignore_index && tg >= 0 && tg < Cm) ? (int)tg : -1;
-            }
+            ti = tr.get(w);
             if (ti < 0) {  // ignored: sorts after every probability, never kept
               prow[w] = 2.f;
               continue;
@@ -1327,10 +987,10 @@ __global__ __launch_bounds__(HD_T) void ohem_head_kernel(OhemHeadArgs a) {
           } else {
             pv = prow[w];
             if (!(pv <= thr && pv < 1.5f)) continue;  // not kept (2.0: ignored, also under inf)
-            ti = t8 ? (int)tgt8[(size_t)h * W + w] : (int)trow[w];
+            ti = tr.t8 ? (int)tr.tgt8[(size_t)h * tl.W + w] : (int)tr.trow[w];
             ti = min(max(ti, 0), Cm - 1);  // (a kept pixel is a labelled one: already in range)
           }
-          const Lerp lw = ac_lerp(w, Wl, W, sw);
+          const Lerp lw = ac_lerp(w, tl.Wl, tl.W, tl.sw);
           const f32x2 w1 = {lw.l1, lw.l1};
           f32x2 e[CP];
 #pragma unroll
@@ -1366,101 +1026,24 @@ __global__ __launch_bounds__(HD_T) void ohem_head_kernel(OhemHeadArgs a) {
           const float wt = s_w[ti];
           loss = fmaf(wt, (mx - lt + __builtin_amdgcn_logf(se)) * HD_LN2, loss);
           wsum += wt;
-          const f32x2 k0 = {lh.l0 * lw.l0, lh.l0 * lw.l1};
-          const f32x2 k1 = {lh.l1 * lw.l0, lh.l1 * lw.l1};
-          const f32x2 iv = {inv * wt, inv * wt};
-#pragma unroll
-          for (int p = 0; p < CP; ++p) {
-            const f32x2 oh = {2 * p == ti ? wt : 0.f, 2 * p + 1 == ti ? wt : 0.f};
-            const f32x2 g = e[p] * iv - oh;
-            const f32x2 gx = {g.x, g.x}, gy = {g.y, g.y};
-            a0[2 * p] = __builtin_elementwise_fma(k0, gx, a0[2 * p]);
-            a1[2 * p] = __builtin_elementwise_fma(k1, gx, a1[2 * p]);
-            if (2 * p + 1 < CT) {
-              a0[2 * p + 1] = __builtin_elementwise_fma(k0, gy, a0[2 * p + 1]);
-              a1[2 * p + 1] = __builtin_elementwise_fma(k1, gy, a1[2 * p + 1]);
-            }
-          }
+          hd_tap_accum_pk<CT>(a0, a1, e, inv, wt, ti, true, lh, lw);
         }
       }
     }
-    float acc00[CT], acc01[CT], acc10[CT], acc11[CT];
-#pragma unroll
-    for (int c = 0; c < CT; ++c) {
-      acc00[c] = a0[c].x;
-      acc01[c] = a0[c].y;
-      acc10[c] = a1[c].x;
-      acc11[c] = a1[c].y;
-    }
-    if (active) {
-      if (t == Wl - 1) {  // i1(w) == i0(w) on the last column: both taps are column t
-#pragma unroll
-        for (int c = 0; c < CT; ++c) {
-          acc00[c] += acc01[c];
-          acc10[c] += acc11[c];
-          acc01[c] = acc11[c] = 0.f;
-        }
-      }
-      if (hl1 == hl) {  // last row: both row taps are row hl
-#pragma unroll
-        for (int c = 0; c < CT; ++c) {
-          acc00[c] += acc10[c];
-          acc01[c] += acc11[c];
-          acc10[c] = acc11[c] = 0.f;
-        }
-      }
-    }
-    // ---- hand the (*, t+1) shares to thread t+1 through LDS -------------------------------
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < CT; ++c) {
-      s_L[tid * SL + c] = acc01[c];
-      s_L[((HD_T + 1) + tid) * SL + c] = acc11[c];
-    }
-    __syncthreads();
-    if (active) {
-      float* o0 = g0 + (((size_t)n * Hl + hl) * Wl + t) * ldl;
-      float* o1 = g1 + (((size_t)n * Hl + hl + 1) * Wl + t) * ldl;
-#pragma unroll
-      for (int c = 0; c < CT; ++c) {
-        if (c < Cm) {
-          const float left0 = tid > 0 ? s_L[(tid - 1) * SL + c] : s_carry[c];
-          const float left1 = tid > 0 ? s_L[((HD_T + 1) + tid - 1) * SL + c] : s_carry[CT + c];
-          o0[c] = acc00[c] + left0;
-          if (hl1 != hl) o1[c] = acc10[c] + left1;
-        }
-      }
-    }
-    __syncthreads();
-    if (tid == HD_T - 1) {  // column cb + HD_T starts the next chunk
-#pragma unroll
-      for (int c = 0; c < CT; ++c) {
-        s_carry[c] = acc01[c];
-        s_carry[CT + c] = acc11[c];
-      }
-    }
+    hd_tile_epilogue<CT>(a0, a1, tl, cl, s_L, (HD_T + 1) * SL, SL, s_carry, a.g_raw, g1, ldl, Cm);
   }
-  s_r1[tid] = loss;
-  s_r2[tid] = wsum;
-  s_c1[tid] = nlab;
-  s_c2[tid] = nle;
-  __syncthreads();
-  for (int off = HD_T / 2; off > 0; off >>= 1) {
-    if (tid < off) {
-      s_r1[tid] += s_r1[tid + off];
-      s_r2[tid] += s_r2[tid + off];
-      s_c1[tid] += s_c1[tid + off];
-      s_c2[tid] += s_c2[tid + off];
-    }
-    __syncthreads();
-  }
+  s_r[0][tid] = loss;
+  s_r[1][tid] = wsum;
+  s_c[0][tid] = nlab;
+  s_c[1][tid] = nle;
+  hd_block_reduce<2, 2>(s_r, s_c, tid);
   if (tid == 0) {
-    const size_t pi = (size_t)n * Hl + hl;
-    a.part[2 * pi] = s_r1[0];
-    a.part[2 * pi + 1] = s_r2[0];
+    const size_t pi = (size_t)tl.n * tl.Hl + tl.hl;
+    a.part[2 * pi] = s_r[0][0];
+    a.part[2 * pi + 1] = s_r[1][0];
     if (PASS == 1) {
-      if (s_c1[0]) atomicAdd(&a.counts[0], (unsigned long long)s_c1[0]);
-      if (s_c2[0]) atomicAdd(&a.counts[1], (unsigned long long)s_c2[0]);
+      if (s_c[0][0]) atomicAdd(&a.counts[0], (unsigned long long)s_c[0][0]);
+      if (s_c[1][0]) atomicAdd(&a.counts[1], (unsigned long long)s_c[1][0]);
     }
   }
 }
@@ -1470,46 +1053,12 @@ __global__ void ohem_head_zero_kernel(unsigned long long* counts) {
   if (threadIdx.x < 2) counts[threadIdx.x] = 0ull;
 }
 
-// out2 = (weighted mean loss, sum of kept weights) as ce_head_finalize_kernel; with thr given
-// (pass 2) nothing is written when *thr is bit-equal to thresh
-__global__ __launch_bounds__(256) void ohem_head_finalize_kernel(const float* part, int P,
-                                                                 const float* thr, float thresh,
-                                                                 float* out) {
-  if (thr && __float_as_uint(*thr) == __float_as_uint(thresh)) return;
-  __shared__ double r1[256], r2[256];
-  double s1 = 0.0, s2 = 0.0;
-  for (int p = threadIdx.x; p < P; p += 256) {
-    s1 += part[2 * p];
-    s2 += part[2 * p + 1];
-  }
-  r1[threadIdx.x] = s1;
-  r2[threadIdx.x] = s2;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (threadIdx.x < off) {
-      r1[threadIdx.x] += r1[threadIdx.x + off];
-      r2[threadIdx.x] += r2[threadIdx.x + off];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    out[0] = r2[0] > 0 ? (float)(r1[0] / r2[0]) : NAN;
-    out[1] = (float)r2[0];
-  }
-}
-
-template <int CT, bool EXACT, int PASS>
-static void ohem_head_launch_dt(const OhemHeadArgs& a, int dtype, dim3 grid, hipStream_t st) {
-  if (dtype == DT_F32) prof_launch((ohem_head_kernel<float, CT, EXACT, PASS>), grid, HD_T, 0, st, a);
-  else if (dtype == DT_F16) prof_launch((ohem_head_kernel<f16, CT, EXACT, PASS>), grid, HD_T, 0, st, a);
-  else prof_launch((ohem_head_kernel<bf16, CT, EXACT, PASS>), grid, HD_T, 0, st, a);
-}
 template <int PASS>
-static void ohem_head_launch_c(const OhemHeadArgs& a, int dtype, dim3 grid, hipStream_t st) {
-  if (a.C == 19) ohem_head_launch_dt<19, true, PASS>(a, dtype, grid, st);
-  else if (a.C == 2) ohem_head_launch_dt<2, true, PASS>(a, dtype, grid, st);
-  else if (a.C <= 8) ohem_head_launch_dt<8, false, PASS>(a, dtype, grid, st);
-  else ohem_head_launch_dt<HD_CMAX, false, PASS>(a, dtype, grid, st);
+static void ohem_head_launch(const OhemHeadArgs& a, int dtype, dim3 grid, hipStream_t st) {
+  hd_dispatch(a.C, dtype, [&](auto i) {
+    using I = decltype(i);
+    prof_launch((ohem_head_kernel<typename I::T, I::CT, I::EXACT, PASS>), grid, HD_T, 0, st, a);
+  });
 }
 
 bool ohem_head_ok(int C) { return C >= 1 && C <= HD_CMAX; }
@@ -1531,9 +1080,9 @@ int ohem_head(const OhemHeadArgs& a, long long min_kept, unsigned* work, float* 
     ProfScope ps(PK_CE, st, (dtype == DT_F32 ? 4.0 : 2.0) * M * a.C + (a.tgt8 ? 1.0 : 8.0) * npix +
                                 4.0 * npix + 2.0 * 4.0 * M * a.C, 0.0);
     prof_launch(ohem_head_zero_kernel, 1, 64, 0, st, a.counts);
-    ohem_head_launch_c<1>(a, dtype, grid, st);
+    ohem_head_launch<1>(a, dtype, grid, st);
     if (int rc = check_launch("ohem_head (pass 1)")) return rc;
-    prof_launch(ohem_head_finalize_kernel, 1, 256, 0, st, a.part, P, (const float*)nullptr,
+    prof_launch(ce_head_finalize_kernel, 1, 256, 0, st, a.part, P, (const float*)nullptr,
                 a.thresh, out2);
     if (int rc = check_launch("ohem_head_finalize")) return rc;
   }
@@ -1541,9 +1090,9 @@ int ohem_head(const OhemHeadArgs& a, long long min_kept, unsigned* work, float* 
                                   const_cast<float*>(a.thr), st))
     return rc;
   ProfScope ps(PK_CE, st, 4.0 * npix, 0.0);
-  ohem_head_launch_c<2>(a, dtype, grid, st);
+  ohem_head_launch<2>(a, dtype, grid, st);
   if (int rc = check_launch("ohem_head (pass 2)")) return rc;
-  prof_launch(ohem_head_finalize_kernel, 1, 256, 0, st, a.part, P, a.thr, a.thresh, out2);
+  prof_launch(ce_head_finalize_kernel, 1, 256, 0, st, a.part, P, a.thr, a.thresh, out2);
   return check_launch("ohem_head_finalize (pass 2)");
 }
 
