@@ -200,6 +200,7 @@ SIGNATURES = {
     "fscnn_dropout": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_ull, c_vp, c_ull,
                               c_float, c_vp, c_vp, c_vp, c_int, c_vp]),
     "fscnn_dw3x3_parts": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "fscnn_dw3x3_ct_width": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
     "fscnn_dw3x3_fwd_train": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp,
                                       c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                       c_float, c_vp, c_vp, c_vp, c_vp, P_int, c_vp]),

@@ -1624,6 +1624,11 @@ int fscnn_dw3x3_parts(int N, int H, int W, int C, int stride, int dtype, int dgr
   return dw_parts(N, (H - 1) / stride + 1, (W - 1) / stride + 1, C, dtype, stride);
 }
 
+int fscnn_dw3x3_ct_width(int N, int H, int W, int C, int stride, int dtype) {
+  if (dw_train_check("fscnn_dw3x3_ct_width", dtype, N, H, W, C, stride)) return -1;
+  return dw_ct_width(N, (H - 1) / stride + 1, (W - 1) / stride + 1, W, C, dtype, stride);
+}
+
 int fscnn_dw3x3_fwd_train(const void* x, int dtype, int N, int H, int W, int C, int stride,
                           const float* w, const float* in_scale, const float* in_shift, void* z,
                           float* part, unsigned* counters, double* tsum, const float* gamma,

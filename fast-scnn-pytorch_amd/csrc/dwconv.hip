@@ -15,10 +15,16 @@
 // wgrad = same tiles; a workgroup walks tpb tiles along a row band, accumulates 9 x V taps per
 // thread, reduces its 32 pixel groups in fixed order -> partial [part][9][C] (two-pass reducer).
 //
-// Roofline: HBM-bound.  Algorithmic bytes per layer = e*(N*C*Hi*Wi + N*C*Ho*Wo) + 9*C*4,
-// flops = 18*N*C*Ho*Wo.
+// Roofline: algorithmic bytes per layer = e*(N*C*Hi*Wi + N*C*Ho*Wo) + 9*C*4, flops =
+// 18*N*C*Ho*Wo: HBM-bound on paper, but as built the tile kernels are bound
+// by VALU issue, not by HBM -- of the ~1,430 VALU instructions a wave of the bf16 stride-1 train
+// forward executed, 226 were the convolution's FMAs; the rest was index arithmetic, 64-bit
+// addresses and edge guards (SQ counters and static counts: profiles/dw_instruction_budget.md).
+// The compile-time-cbv kernels below cut that to ~990 (interior tile) / ~1,215 (border tile);
+// what remains is the lazy BN+ReLU of 48 elements, the bf16 unpacks and the statistics.
 #include "bn_finish.hpp"
 
+#include <initializer_list>
 #include <optional>
 
 namespace fscnn {
@@ -135,34 +141,160 @@ __device__ __forceinline__ void dw_stage(uint4* s_in, const T* x, int H, int W, 
   }
 }
 
-// ---- forward (and stride-1 dgrad with FLIP) -------------------------------------------------
-// TL: the launch finishes its BN in the last workgroups (a.tail_ink; a separate instantiation so
-// the other launches keep their register budget)
-template <typename T, int S, bool FLIP, bool IT, bool BR = false, bool TL = false>
-__global__ __launch_bounds__(256, 3) void dw_fwd_kernel(DwArgs a, int cbv) {
+// ---- compile-time channel-chunk width (CBV > 0) ------------------------------------------------
+// The widths the network uses (C = 32, 48, >= 64) get instantiations with cbv, the workgroup size
+// 32 * cbv and the tile all constant: thread indices, the staging walk and every LDS offset fold
+// to constants, the tile's 64-bit base is formed once on the scalar side and each lane carries a
+// 32-bit byte offset from it (the host checks that a tile's span fits 31 bits and that the grid's
+// tile count fits 32), and a tile that lies wholly inside the image (a workgroup-uniform test)
+// takes a path with no clamps, selects or ragged-edge guards.  The terms that path drops are the
+// ones the guarded code adds as 0.f or skips, so every stored value is the same.  CBV = 0 is the
+// run-time-cbv, bounds-checked kernel for every other C (and FSCNN_DW_GENERIC=1).
+
+// dw_tile in 32-bit arithmetic
+__device__ __forceinline__ void dw_tile32(int& cx, int& cy, int& cz) {
+  const unsigned gx = gridDim.x, gy = gridDim.y, gz = gridDim.z;
+  const unsigned T = gx * gy * gz;
+  unsigned L = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
+  if ((T & 7u) == 0) L = (L & 7u) * (T >> 3) + (L >> 3);
+  cx = (int)(L % gx);
+  const unsigned r = L / gx;
+  cy = (int)(r % gy);
+  cz = (int)(r / gy);
+}
+
+// 4 per-channel fp32 values from channel c (c % 4 == 0); VEC: one 16-B load (the compile-time-cbv
+// kernels: the host checks that the row is 16-B aligned)
+template <bool VEC>
+__device__ __forceinline__ void ch4(const float* p, int c, float (&v)[4]) {
+  if constexpr (VEC) {
+    const float4 t = *reinterpret_cast<const float4*>(p + c);
+    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = p[c + j];
+  }
+}
+
+// multiply kept out of a following add (the guarded code's `ok ? d * d : 0.f` cannot contract)
+__device__ __forceinline__ float mul_rn(float x, float y) {
+#pragma clang fp contract(off)
+  return x * y;
+}
+
+// dw_stage with cbv = CBV: xb is the byte address of the tile's (hi0, wi0) pixel at the chunk's
+// first channel (it may lie outside the tensor; only in-image offsets from it are read), rowb /
+// pixb the bytes per image row / pixel.  A thread's k-th vector is pixel tid / CBV + 32 k of the
+// tile, vector tid % CBV: a constant (row, col) step from its first, with one wrap test.
+// INT: the whole haloed tile is inside the image.
+template <typename T, int S, bool IT, int CBV, bool INT>
+__device__ __forceinline__ void dw_stage_ct(uint4* s_in, const char* xb, uint32_t rowb,
+                                            uint32_t pixb, int H, int W, int hi0, int wi0,
+                                            int cvbase, int tid, const float* isc,
+                                            const float* ish) {
   using G = DwTile<T, S>;
+  constexpr int V = VecW<T>::V;
+  constexpr int NPIX = G::IR * G::IC, DR = 32 / G::IC, DC = 32 % G::IC;
+  const int lv = tid % CBV, pix0 = tid / CBV;
+  float sc[IT ? V : 1], sh[IT ? V : 1];
+  if constexpr (IT) {
+    const int cb = (cvbase + lv) * V;  // 16-B aligned rows (host-checked)
+#pragma unroll
+    for (int j = 0; j < V; j += 4) {
+      const float4 s4 = *reinterpret_cast<const float4*>(isc + cb + j);
+      const float4 h4 = *reinterpret_cast<const float4*>(ish + cb + j);
+      sc[j] = s4.x; sc[j + 1] = s4.y; sc[j + 2] = s4.z; sc[j + 3] = s4.w;
+      sh[j] = h4.x; sh[j + 1] = h4.y; sh[j + 2] = h4.z; sh[j + 3] = h4.w;
+    }
+  }
+  // a position every lane may read: the tile's own corner (interior), else the input pixel of
+  // the tile's first output, which is always inside the image
+  const uint32_t safe = (INT ? 0u : rowb + pixb) + (uint32_t)lv * 16u;
+  uint4 raw[G::LPT];
+  bool okk[G::LPT];
+  int r = pix0 / G::IC, col = pix0 - r * G::IC;
+  uint32_t off = (uint32_t)r * rowb + (uint32_t)col * pixb + (uint32_t)lv * 16u;
+#pragma unroll
+  for (int k = 0; k < G::LPT; ++k) {
+    bool ok = (32 * k + 31 < NPIX) || pix0 + 32 * k < NPIX;
+    if constexpr (!INT)
+      ok = ok && (unsigned)(hi0 + r) < (unsigned)H && (unsigned)(wi0 + col) < (unsigned)W;
+    okk[k] = ok;
+    const uint4 t = *reinterpret_cast<const uint4*>(xb + (ok ? off : safe));
+    if constexpr (INT) raw[k] = t;
+    else raw[k] = sel4(ok, t);
+    const bool wrap = col + DC >= G::IC;
+    col += wrap ? DC - G::IC : DC;
+    r += wrap ? DR + 1 : DR;
+    off += wrap ? (uint32_t)(DR + 1) * rowb - (uint32_t)(G::IC - DC) * pixb
+                : (uint32_t)DR * rowb + (uint32_t)DC * pixb;
+  }
+#pragma unroll
+  for (int k = 0; k < G::LPT; ++k) {
+    if ((32 * k + 31 < NPIX) || pix0 + 32 * k < NPIX) {
+      uint4 v = raw[k];
+      if constexpr (IT) {
+        if constexpr (INT) v = bnrelu_vec<T>(v, sc, sh);
+        else v = sel4(okk[k], bnrelu_vec<T>(v, sc, sh));
+      }
+      s_in[tid + k * 32 * CBV] = v;
+    }
+  }
+}
+
+// ---- forward (and stride-1 dgrad with FLIP) -------------------------------------------------
+// One tile.  CBV = 0: run-time cbv (cbv_rt), every access bounds-checked.  CBV > 0: see above;
+// INT: the haloed input tile and the output tile lie wholly inside the image.
+template <typename T, int S, bool FLIP, bool IT, bool BR, int CBV, bool INT>
+__device__ __forceinline__ void dw_fwd_body(const DwArgs& a, int cbv_rt, uint4* s_dyn, int bx,
+                                            int by, int bz, int n, int th0, int tw0) {
+  using G = DwTile<T, S>;
+  constexpr bool CT = CBV > 0;
+  const int cbv = CT ? CBV : cbv_rt;
   // LDS sized per launch (dw_shm): the staged tile of cbv channel vectors + the reduction rows
-  extern __shared__ __attribute__((aligned(16))) uint4 s_dyn[];
   uint4* s_in = s_dyn;
   float* s_red = reinterpret_cast<float*>(s_dyn + G::IR * G::IC * cbv);
   const int tid = threadIdx.x, nthr = blockDim.x;
   const int QB = cbv * G::QPV;                 // quads per workgroup
   const int q = tid % QB, grp = tid / QB;
   const int gx = grp % G::GX, gy = grp / G::GX;
-  int bx, by, bz;
-  dw_tile(bx, by, bz);
-  const int tiles_h = cdiv(a.Ho, G::TH);
-  const int n = bz / tiles_h;
-  const int th0 = (bz - n * tiles_h) * G::TH, tw0 = by * G::TW;
   const int c0 = bx * cbv * VecW<T>::V + q * 4;  // first channel of the thread's quad
+  // CT: output-side addressing = the tile's base (y and the dgrad's z share the geometry) + a
+  // 32-bit byte offset per lane
+  const uint32_t orowb = (uint32_t)a.Wo * (uint32_t)a.C * (uint32_t)sizeof(T);
+  const uint32_t opixb = (uint32_t)a.C * (uint32_t)sizeof(T);
+  const size_t obase = ((((size_t)n * a.Ho + th0) * a.Wo + tw0) * a.C + (size_t)bx * cbv * VecW<T>::V) * sizeof(T);
+  const uint32_t olane = (uint32_t)(gy * G::HS) * orowb + (uint32_t)(gx * G::WS) * opixb +
+                         (uint32_t)q * 4u * (uint32_t)sizeof(T);
   stamp(a.stamps, 0);
-  dw_stage<T, S, IT>(s_in, (const T*)a.x, a.H, a.W, a.C, n, th0 * S - 1, tw0 * S - 1,
-                     bx * cbv, cbv, tid, nthr, a.in_scale, a.in_shift);
   float wt[9][4];
+  if constexpr (CT) {
+    const long long xoff = ((((long long)n * a.H + (th0 * S - 1)) * a.W + (tw0 * S - 1)) * a.C +
+                            (long long)bx * cbv * VecW<T>::V) * (long long)sizeof(T);
+    dw_stage_ct<T, S, IT, CBV, INT>(s_in, (const char*)a.x + xoff,
+                                    (uint32_t)a.W * (uint32_t)a.C * (uint32_t)sizeof(T),
+                                    (uint32_t)a.C * (uint32_t)sizeof(T), a.H, a.W, th0 * S - 1,
+                                    tw0 * S - 1, bx * cbv, tid, a.in_scale, a.in_shift);
+    // the quad's 36 taps as 9 16-B loads (rows of 4 channels x 9 taps are 16-B aligned)
+    const float4* wp = reinterpret_cast<const float4*>(a.w + (size_t)c0 * 9);
 #pragma unroll
-  for (int j = 0; j < 4; ++j)
+    for (int i = 0; i < 9; ++i) {
+      const float4 t4 = wp[i];
+      const float tt[4] = {t4.x, t4.y, t4.z, t4.w};
 #pragma unroll
-    for (int t = 0; t < 9; ++t) wt[FLIP ? 8 - t : t][j] = a.w[(size_t)(c0 + j) * 9 + t];
+      for (int e = 0; e < 4; ++e) {
+        const int f = 4 * i + e;  // = j * 9 + tap
+        wt[FLIP ? 8 - f % 9 : f % 9][f / 9] = tt[e];
+      }
+    }
+  } else {
+    dw_stage<T, S, IT>(s_in, (const T*)a.x, a.H, a.W, a.C, n, th0 * S - 1, tw0 * S - 1,
+                       bx * cbv, cbv, tid, nthr, a.in_scale, a.in_shift);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int t = 0; t < 9; ++t) wt[FLIP ? 8 - t : t][j] = a.w[(size_t)(c0 + j) * 9 + t];
+  }
   __syncthreads();
   stamp(a.stamps, 1);
 
@@ -198,24 +330,42 @@ __global__ __launch_bounds__(256, 3) void dw_fwd_kernel(DwArgs a, int cbv) {
         }
       }
     }
+    if constexpr (CT) {
+      // with constant LDS offsets nothing else holds the FMAs of a row in front of the next row's
+      // loads (the barrier above orders memory operations only): the accumulators pass through
+      // an empty asm, so the row's window is consumed before the next one is read
+#pragma unroll
+      for (int r = 0; r < G::HS; ++r)
+#pragma unroll
+        for (int p = 0; p < G::WS; ++p) {
+          // (as the register pairs of the packed FMAs)
+          typedef float pair_t __attribute__((ext_vector_type(2)));
+          pair_t lo = {acc[r][p][0], acc[r][p][1]}, hi = {acc[r][p][2], acc[r][p][3]};
+          asm volatile("" : "+v"(lo), "+v"(hi));
+          acc[r][p][0] = lo.x; acc[r][p][1] = lo.y; acc[r][p][2] = hi.x; acc[r][p][3] = hi.y;
+        }
+    }
   }
+  // (the epilogue's per-channel loads stay behind the FMA phase)
+  asm volatile("" ::: "memory");
 
   const int ho0 = th0 + gy * G::HS, wo0 = tw0 + gx * G::WS;
-  const int nrow = max(0, min(G::HS, a.Ho - ho0)), ncol = max(0, min(G::WS, a.Wo - wo0));
+  const int nrow = INT ? G::HS : max(0, min(G::HS, a.Ho - ho0));
+  const int ncol = INT ? G::WS : max(0, min(G::WS, a.Wo - wo0));
   {
-    float sc[4], sh[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      sc[j] = a.scale ? a.scale[c0 + j] : 1.f;
-      sh[j] = a.scale ? a.shift[c0 + j] : 0.f;
+    float sc[4] = {1.f, 1.f, 1.f, 1.f}, sh[4] = {0.f, 0.f, 0.f, 0.f};
+    if (a.scale) {
+      ch4<CT>(a.scale, c0, sc);
+      ch4<CT>(a.shift, c0, sh);
     }
+    char* const ytile = (char*)a.y + obase;
 #pragma unroll
     for (int r = 0; r < G::HS; ++r) {
-      if (r >= nrow) continue;
+      if (!INT && r >= nrow) continue;
       T* yb = (T*)a.y + (((size_t)n * a.Ho + ho0 + r) * a.Wo + wo0) * a.C + c0;
 #pragma unroll
       for (int p = 0; p < G::WS; ++p) {
-        if (p >= ncol) continue;
+        if (!INT && p >= ncol) continue;
         float o[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -223,7 +373,10 @@ __global__ __launch_bounds__(256, 3) void dw_fwd_kernel(DwArgs a, int cbv) {
           o[j] = a.relu ? fmaxf(t, 0.f) : t;
           acc[r][p][j] = round_as<T>(o[j]);  // (the statistics below: of the stored value)
         }
-        quad_st(yb + (size_t)p * a.C, o);
+        if constexpr (CT)
+          quad_st(reinterpret_cast<T*>(ytile + (olane + (uint32_t)r * orowb + (uint32_t)p * opixb)), o);
+        else
+          quad_st(yb + (size_t)p * a.C, o);
       }
     }
   }
@@ -232,27 +385,35 @@ __global__ __launch_bounds__(256, 3) void dw_fwd_kernel(DwArgs a, int cbv) {
     // ---- stride-1 dgrad: BN-backward partial sums of the stored dx (it is that BN's dy) -----
     const BnBwdPart& b = a.bs;
     const bool m2 = b.mode == 2;
-    float bm[4], bi[4], bsc[4], bsh[4], s1[4], s2[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      bm[j] = b.mean[c0 + j];
-      bi[j] = b.invstd[c0 + j];
-      bsc[j] = m2 ? b.scale[c0 + j] : 0.f;  // mode 0: mask fmaf(z, 0, 1) > 0 always
-      bsh[j] = m2 ? b.shift[c0 + j] : 1.f;
-      s1[j] = s2[j] = 0.f;
+    // mode 0: mask fmaf(z, 0, 1) > 0 always
+    float bm[4], bi[4], bsc[4] = {0.f, 0.f, 0.f, 0.f}, bsh[4] = {1.f, 1.f, 1.f, 1.f}, s1[4], s2[4];
+    ch4<CT>(b.mean, c0, bm);
+    ch4<CT>(b.invstd, c0, bi);
+    if (m2) {
+      ch4<CT>(b.scale, c0, bsc);
+      ch4<CT>(b.shift, c0, bsh);
     }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s1[j] = s2[j] = 0.f;
+    const char* const ztile = (const char*)b.z + obase;
 #pragma unroll
     for (int r = 0; r < G::HS; ++r) {
       float z[G::WS][4];  // one output row of z per batch of loads
 #pragma unroll
       for (int p = 0; p < G::WS; ++p) {
-        const bool ok = r < nrow && p < ncol;
-        const size_t pix = ok ? ((size_t)n * a.Ho + ho0 + r) * a.Wo + wo0 + p : 0;
-        quad_ld((const T*)b.z + pix * a.C + c0, z[p]);
+        const bool ok = INT || (r < nrow && p < ncol);
+        if constexpr (CT) {
+          // (not ok: the tile's first pixel, which exists)
+          const uint32_t zo = (uint32_t)r * orowb + (uint32_t)p * opixb + olane;
+          quad_ld(reinterpret_cast<const T*>(ztile + (ok ? zo : (uint32_t)q * 4u * (uint32_t)sizeof(T))), z[p]);
+        } else {
+          const size_t pix = ok ? ((size_t)n * a.Ho + ho0 + r) * a.Wo + wo0 + p : 0;
+          quad_ld((const T*)b.z + pix * a.C + c0, z[p]);
+        }
       }
 #pragma unroll
       for (int p = 0; p < G::WS; ++p) {
-        const bool ok = r < nrow && p < ncol;
+        const bool ok = INT || (r < nrow && p < ncol);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           float gv = round_as<T>(acc[r][p][j]);
@@ -281,11 +442,6 @@ __global__ __launch_bounds__(256, 3) void dw_fwd_kernel(DwArgs a, int cbv) {
       }
     }
     stamp(a.stamps, 3);
-    if constexpr (TL)
-      tail_finish<false>(b.part, gridDim.y * gridDim.z, a.C, bz * gridDim.y + by,
-                         bx * cbv * VecW<T>::V, cbv * VecW<T>::V, bx, a.tail,
-                         reinterpret_cast<double*>(s_dyn));
-    stamp(a.stamps, 4);
     return;
   }
   if (a.part == nullptr) return;
@@ -319,7 +475,7 @@ __global__ __launch_bounds__(256, 3) void dw_fwd_kernel(DwArgs a, int cbv) {
 #pragma unroll
       for (int p = 0; p < G::WS; ++p) {
         const float d = acc[r][p][j] - mean[j];
-        m2 += (r < nrow && p < ncol) ? d * d : 0.f;
+        m2 += (r < nrow && p < ncol) ? mul_rn(d, d) : 0.f;  // (never fma(d, d, m2))
       }
     s_red[(grp * QB + q) * 4 + j] = m2;
   }
@@ -336,10 +492,42 @@ __global__ __launch_bounds__(256, 3) void dw_fwd_kernel(DwArgs a, int cbv) {
     }
   }
   stamp(a.stamps, 3);
-  if constexpr (TL)
-    tail_finish<true>(a.part, gridDim.y * gridDim.z, a.C, bz * gridDim.y + by,
-                      bx * cbv * VecW<T>::V, cbv * VecW<T>::V, bx, a.tail,
-                      reinterpret_cast<double*>(s_dyn));
+}
+
+// TL: the launch finishes its BN in the last workgroups (a.tail_ink; a separate instantiation so
+// the other launches keep their register budget)
+template <typename T, int S, bool FLIP, bool IT, bool BR = false, bool TL = false, int CBV = 0>
+__global__ __launch_bounds__(256, 3) void dw_fwd_kernel(DwArgs a, int cbv_rt) {
+  using G = DwTile<T, S>;
+  extern __shared__ __attribute__((aligned(16))) uint4 s_dyn[];
+  int bx, by, bz;
+  if constexpr (CBV > 0) dw_tile32(bx, by, bz);
+  else dw_tile(bx, by, bz);
+  const int tiles_h = cdiv(a.Ho, G::TH);
+  const int n = bz / tiles_h;
+  const int th0 = (bz - n * tiles_h) * G::TH, tw0 = by * G::TW;
+  if constexpr (CBV > 0) {
+    // workgroup-uniform: one whole-path branch, never a branch around a load
+    const bool inside = th0 >= 1 && tw0 >= 1 && th0 * S - 1 + G::IR <= a.H &&
+                        tw0 * S - 1 + G::IC <= a.W && th0 + G::TH <= a.Ho && tw0 + G::TW <= a.Wo;
+    if (inside) dw_fwd_body<T, S, FLIP, IT, BR, CBV, true>(a, cbv_rt, s_dyn, bx, by, bz, n, th0, tw0);
+    else dw_fwd_body<T, S, FLIP, IT, BR, CBV, false>(a, cbv_rt, s_dyn, bx, by, bz, n, th0, tw0);
+  } else {
+    dw_fwd_body<T, S, FLIP, IT, BR, 0, false>(a, cbv_rt, s_dyn, bx, by, bz, n, th0, tw0);
+  }
+  if (!BR && a.part == nullptr) return;
+  // the BN finish of the records just written, in the launch's last workgroups
+  if constexpr (TL) {
+    const int cbv = CBV > 0 ? CBV : cbv_rt;
+    if constexpr (BR)
+      tail_finish<false>(a.bs.part, gridDim.y * gridDim.z, a.C, bz * gridDim.y + by,
+                         bx * cbv * VecW<T>::V, cbv * VecW<T>::V, bx, a.tail,
+                         reinterpret_cast<double*>(s_dyn));
+    else
+      tail_finish<true>(a.part, gridDim.y * gridDim.z, a.C, bz * gridDim.y + by,
+                        bx * cbv * VecW<T>::V, cbv * VecW<T>::V, bx, a.tail,
+                        reinterpret_cast<double*>(s_dyn));
+  }
   stamp(a.stamps, 4);
 }
 
@@ -373,20 +561,62 @@ int dw_parts(int N, int Ho, int Wo, int C, int dtype, int stride) {
   return (int)(g.y * g.z);
 }
 
-template <typename T, bool FLIP, bool IT, bool BR>
-static void dw_launch_fwd_t(const DwArgs& a, dim3 grid, int nthr, int cbv, hipStream_t st) {
+// FSCNN_DW_GENERIC=1: every tile launch on the run-time-cbv, bounds-checked kernels (A/B;
+// tests/test_gpu_dw_paths.py)
+static bool dw_generic() {
+  static const bool on = env_on("FSCNN_DW_GENERIC", false);
+  return on;
+}
+
+static bool dw_al16(const void* p) { return (uintptr_t)p % 16 == 0; }
+
+// whether a launch may take the compile-time-cbv kernels: an instantiated width, the grid's tile
+// count in 32 bits, a tile's span of either map (<= 18 rows + a tile's width) in 31 bits of byte
+// offset, and 16-B aligned per-channel rows for their vector loads
+static bool dw_ct_ok(int cbv, int V, dim3 grid, int W, int Wo, int C,
+                     std::initializer_list<const float*> rows) {
+  if (dw_generic()) return false;
+  if (!(cbv == 8 || cbv == 6 || (cbv == 4 && V == 8))) return false;
+  if ((unsigned long long)grid.x * grid.y * grid.z >= (1ull << 31)) return false;
+  if (20LL * ((W > Wo ? W : Wo) + 80LL) * C * 4 >= (1LL << 31)) return false;
+  for (const float* r : rows)
+    if (!dw_al16(r)) return false;
+  return true;
+}
+
+int dw_ct_width(int N, int Ho, int Wo, int W, int C, int dtype, int stride) {
+  const int V = dtype == DT_F32 ? 4 : 8;
+  int cbv;
+  const dim3 g = dw_grid(N, Ho, Wo, C, V, stride, cbv);
+  return dw_ct_ok(cbv, V, g, W, Wo, C, {}) ? cbv : 0;
+}
+
+template <typename T, bool FLIP, bool IT, bool BR, int CBV>
+static void dw_launch_fwd_c(const DwArgs& a, dim3 grid, int nthr, int cbv, hipStream_t st) {
   if constexpr (BR) {  // stride-1 dgrad with BN-backward partials
-    if (a.tail_ink) prof_launch(dw_fwd_kernel<T, 1, true, false, true, true>, grid, nthr, dw_shm<T, 1>(cbv), st, a, cbv);
-    else prof_launch(dw_fwd_kernel<T, 1, true, false, true>, grid, nthr, dw_shm<T, 1>(cbv), st, a, cbv);
+    if (a.tail_ink) prof_launch(dw_fwd_kernel<T, 1, true, false, true, true, CBV>, grid, nthr, dw_shm<T, 1>(cbv), st, a, cbv);
+    else prof_launch(dw_fwd_kernel<T, 1, true, false, true, false, CBV>, grid, nthr, dw_shm<T, 1>(cbv), st, a, cbv);
     return;
   }
   if (!FLIP && a.tail_ink) {  // train forward with the in-kernel BN finish
-    if (a.stride == 1) prof_launch(dw_fwd_kernel<T, 1, false, IT, false, true>, grid, nthr, dw_shm<T, 1>(cbv), st, a, cbv);
-    else prof_launch(dw_fwd_kernel<T, 2, false, IT, false, true>, grid, nthr, dw_shm<T, 2>(cbv), st, a, cbv);
+    if (a.stride == 1) prof_launch(dw_fwd_kernel<T, 1, false, IT, false, true, CBV>, grid, nthr, dw_shm<T, 1>(cbv), st, a, cbv);
+    else prof_launch(dw_fwd_kernel<T, 2, false, IT, false, true, CBV>, grid, nthr, dw_shm<T, 2>(cbv), st, a, cbv);
     return;
   }
-  if (a.stride == 1) prof_launch(dw_fwd_kernel<T, 1, FLIP, IT>, grid, nthr, dw_shm<T, 1>(cbv), st, a, cbv);
-  else prof_launch(dw_fwd_kernel<T, 2, FLIP, IT>, grid, nthr, dw_shm<T, 2>(cbv), st, a, cbv);
+  if (a.stride == 1) prof_launch(dw_fwd_kernel<T, 1, FLIP, IT, false, false, CBV>, grid, nthr, dw_shm<T, 1>(cbv), st, a, cbv);
+  else prof_launch(dw_fwd_kernel<T, 2, FLIP, IT, false, false, CBV>, grid, nthr, dw_shm<T, 2>(cbv), st, a, cbv);
+}
+
+template <typename T, bool FLIP, bool IT, bool BR>
+static void dw_launch_fwd_t(const DwArgs& a, dim3 grid, int nthr, int cbv, hipStream_t st) {
+  const bool ct = dw_ct_ok(cbv, VecW<T>::V, grid, a.W, a.Wo, a.C,
+                           {a.w, a.in_scale, a.in_shift, a.scale, a.shift, a.bs.mean, a.bs.invstd,
+                            a.bs.scale, a.bs.shift});
+  if (ct && cbv == 8) return dw_launch_fwd_c<T, FLIP, IT, BR, 8>(a, grid, nthr, cbv, st);
+  if (ct && cbv == 6) return dw_launch_fwd_c<T, FLIP, IT, BR, 6>(a, grid, nthr, cbv, st);
+  if constexpr (sizeof(T) == 2)
+    if (ct && cbv == 4) return dw_launch_fwd_c<T, FLIP, IT, BR, 4>(a, grid, nthr, cbv, st);
+  dw_launch_fwd_c<T, FLIP, IT, BR, 0>(a, grid, nthr, cbv, st);
 }
 
 template <bool FLIP, bool IT, bool BR = false>
@@ -715,16 +945,77 @@ int dw_dgrad_parts(int N, int H, int W, int C, int dtype, int stride) {
 
 // ---- weight gradient: per-workgroup partial [part][9][C] --------------------------------------
 // grid: x = channel chunk, y = groups of tpb column tiles, z = N * row bands; part = (z, y).
-template <typename T, int S, bool IT>
-__global__ __launch_bounds__(256, 2) void dw_wgrad_kernel(DwBwdArgs a, int cbv, int tpb) {
+// one tile's loads: dy of the thread's outputs into g (zero outside the map), then -- after the
+// barrier that ends the previous tile's LDS reads -- the haloed x tile into LDS.  CBV / INT as in
+// dw_fwd_body.
+template <typename T, int S, bool IT, int CBV, bool INT>
+__device__ __forceinline__ void dw_wgrad_load(const DwBwdArgs& a, int cbv, uint4* s_in,
+                                              float (&g)[DwTile<T, S>::HS][DwTile<T, S>::WS][4],
+                                              int bx, int n, int th0, int tw0, int q, int gx, int gy,
+                                              int c0, int nrow_b) {
+  using G = DwTile<T, S>;
+  constexpr bool CT = CBV > 0;
+  const int tid = threadIdx.x, nthr = blockDim.x;
+  const int ho0 = th0 + gy * G::HS, wo0 = tw0 + gx * G::WS;
+  const int nrow = INT ? G::HS : nrow_b;
+  const int ncol = INT ? G::WS : max(0, min(G::WS, a.Wo - wo0));
+  // dy of the thread's outputs (clamped + selected), issued with the tile loads
+  const uint32_t orowb = (uint32_t)a.Wo * (uint32_t)a.C * (uint32_t)sizeof(T);
+  const uint32_t opixb = (uint32_t)a.C * (uint32_t)sizeof(T);
+  const size_t obase = ((((size_t)n * a.Ho + th0) * a.Wo + tw0) * a.C + (size_t)bx * cbv * VecW<T>::V) * sizeof(T);
+  const uint32_t qb = (uint32_t)q * 4u * (uint32_t)sizeof(T);
+  const uint32_t olane = (uint32_t)(gy * G::HS) * orowb + (uint32_t)(gx * G::WS) * opixb + qb;
+  const T* gb = (const T*)a.dy + c0;
+#pragma unroll
+  for (int r = 0; r < G::HS; ++r)
+#pragma unroll
+    for (int p = 0; p < G::WS; ++p) {
+      const bool ok = INT || (r < nrow && p < ncol);
+      if constexpr (CT) {
+        // (not ok: the tile's first pixel, which exists)
+        const uint32_t go = (uint32_t)r * orowb + (uint32_t)p * opixb + olane;
+        quad_ld(reinterpret_cast<const T*>((const char*)a.dy + obase + (size_t)(ok ? go : qb)), g[r][p]);
+      } else {
+        const size_t off = ok ? (((size_t)n * a.Ho + ho0 + r) * a.Wo + wo0 + p) * a.C : 0;
+        quad_ld(gb + off, g[r][p]);
+      }
+    }
+  if constexpr (!INT) {
+#pragma unroll
+    for (int r = 0; r < G::HS; ++r)
+#pragma unroll
+      for (int p = 0; p < G::WS; ++p) {
+        const bool ok = r < nrow && p < ncol;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) g[r][p][j] = ok ? g[r][p][j] : 0.f;
+      }
+  }
+  __syncthreads();  // previous tile's LDS reads are done
+  if constexpr (CT) {
+    const long long xoff = ((((long long)n * a.H + (th0 * S - 1)) * a.W + (tw0 * S - 1)) * a.C +
+                            (long long)bx * cbv * VecW<T>::V) * (long long)sizeof(T);
+    dw_stage_ct<T, S, IT, CBV, INT>(s_in, (const char*)a.x + xoff,
+                                    (uint32_t)a.W * (uint32_t)a.C * (uint32_t)sizeof(T),
+                                    (uint32_t)a.C * (uint32_t)sizeof(T), a.H, a.W, th0 * S - 1,
+                                    tw0 * S - 1, bx * cbv, tid, a.x_scale, a.x_shift);
+  } else {
+    dw_stage<T, S, IT>(s_in, (const T*)a.x, a.H, a.W, a.C, n, th0 * S - 1, tw0 * S - 1, bx * cbv,
+                       cbv, tid, nthr, a.x_scale, a.x_shift);
+  }
+}
+
+template <typename T, int S, bool IT, int CBV = 0>
+__global__ __launch_bounds__(256, 2) void dw_wgrad_kernel(DwBwdArgs a, int cbv_rt, int tpb) {
   using G = DwTile<T, S>;
   extern __shared__ __attribute__((aligned(16))) uint4 s_in[];  // [IR*IC*cbv] (dw_shm)
-  const int tid = threadIdx.x, nthr = blockDim.x;
+  const int cbv = CBV > 0 ? CBV : cbv_rt;
+  const int tid = threadIdx.x;
   const int QB = cbv * G::QPV;
   const int q = tid % QB, grp = tid / QB;
   const int gx = grp % G::GX, gy = grp / G::GX;
   int bx, by, bz;
-  dw_tile(bx, by, bz);
+  if constexpr (CBV > 0) dw_tile32(bx, by, bz);
+  else dw_tile(bx, by, bz);
   const int tiles_h = cdiv(a.Ho, G::TH), tiles_w = cdiv(a.Wo, G::TW);
   const int n = bz / tiles_h;
   const int th0 = (bz - n * tiles_h) * G::TH;
@@ -739,32 +1030,18 @@ __global__ __launch_bounds__(256, 2) void dw_wgrad_kernel(DwBwdArgs a, int cbv, 
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[t][j] = 0.f;
   const int tw_lo = by * tpb, tw_hi = min(tiles_w, tw_lo + tpb);
+  const bool rows_in = th0 >= 1 && th0 * S - 1 + G::IR <= a.H && th0 + G::TH <= a.Ho;
   for (int twi = tw_lo; twi < tw_hi; ++twi) {
     const int tw0 = twi * G::TW;
-    const int wo0 = tw0 + gx * G::WS;
-    const int ncol = max(0, min(G::WS, a.Wo - wo0));
-    // dy of the thread's outputs (clamped + selected), issued with the tile loads
     float g[G::HS][G::WS][4];
-    const T* gb = (const T*)a.dy + c0;
-#pragma unroll
-    for (int r = 0; r < G::HS; ++r)
-#pragma unroll
-      for (int p = 0; p < G::WS; ++p) {
-        const bool ok = r < nrow && p < ncol;
-        const size_t off = ok ? (((size_t)n * a.Ho + ho0 + r) * a.Wo + wo0 + p) * a.C : 0;
-        quad_ld(gb + off, g[r][p]);
-      }
-#pragma unroll
-    for (int r = 0; r < G::HS; ++r)
-#pragma unroll
-      for (int p = 0; p < G::WS; ++p) {
-        const bool ok = r < nrow && p < ncol;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) g[r][p][j] = ok ? g[r][p][j] : 0.f;
-      }
-    __syncthreads();  // previous tile's LDS reads are done
-    dw_stage<T, S, IT>(s_in, (const T*)a.x, a.H, a.W, a.C, n, th0 * S - 1, tw0 * S - 1, bx * cbv,
-                       cbv, tid, nthr, a.x_scale, a.x_shift);
+    if constexpr (CBV > 0) {
+      // workgroup-uniform whole-path branch; both sides end at the barrier below
+      const bool inside = rows_in && tw0 >= 1 && tw0 * S - 1 + G::IC <= a.W && tw0 + G::TW <= a.Wo;
+      if (inside) dw_wgrad_load<T, S, IT, CBV, true>(a, cbv, s_in, g, bx, n, th0, tw0, q, gx, gy, c0, nrow);
+      else dw_wgrad_load<T, S, IT, CBV, false>(a, cbv, s_in, g, bx, n, th0, tw0, q, gx, gy, c0, nrow);
+    } else {
+      dw_wgrad_load<T, S, IT, 0, false>(a, cbv, s_in, g, bx, n, th0, tw0, q, gx, gy, c0, nrow);
+    }
     __syncthreads();
     const int lr0 = gy * G::HS * S, lc0 = gx * G::WS * S;
 #pragma unroll
@@ -837,10 +1114,18 @@ int dw_wgrad(const DwBwdArgs& a, int dtype, hipStream_t st) {
   const double in_el = (double)a.N * a.C * a.H * a.W, out_el = (double)a.N * a.C * a.Ho * a.Wo;
   ProfScope ps(PK_DW_WGRAD, st, E * (in_el + out_el), 18.0 * out_el);
   const int nthr = cbv * 32;
+  const bool ct = dw_ct_ok(cbv, V, grid, a.W, a.Wo, a.C, {a.x_scale, a.x_shift});
+#define DWW_LAUNCH_C(T, S, CB)                                                                \
+  do {                                                                                        \
+    if (a.x_scale) prof_launch(dw_wgrad_kernel<T, S, true, CB>, grid, nthr, dw_shm<T, S>(cbv), st, a, cbv, tpb); \
+    else prof_launch(dw_wgrad_kernel<T, S, false, CB>, grid, nthr, dw_shm<T, S>(cbv), st, a, cbv, tpb);          \
+  } while (0)
 #define DWW_LAUNCH(T, S)                                                                      \
   do {                                                                                        \
-    if (a.x_scale) prof_launch(dw_wgrad_kernel<T, S, true>, grid, nthr, dw_shm<T, S>(cbv), st, a, cbv, tpb); \
-    else prof_launch(dw_wgrad_kernel<T, S, false>, grid, nthr, dw_shm<T, S>(cbv), st, a, cbv, tpb);          \
+    if (ct && cbv == 8) DWW_LAUNCH_C(T, S, 8);                                                \
+    else if (ct && cbv == 6) DWW_LAUNCH_C(T, S, 6);                                           \
+    else if (ct && cbv == 4 && sizeof(T) == 2) DWW_LAUNCH_C(T, S, (sizeof(T) == 2 ? 4 : 0));  \
+    else DWW_LAUNCH_C(T, S, 0);                                                               \
   } while (0)
   if (dtype == DT_F32) {
     if (a.stride == 1) DWW_LAUNCH(float, 1);
@@ -853,6 +1138,7 @@ int dw_wgrad(const DwBwdArgs& a, int dtype, hipStream_t st) {
     else DWW_LAUNCH(bf16, 2);
   }
 #undef DWW_LAUNCH
+#undef DWW_LAUNCH_C
   return check_launch("dw_wgrad");
 }
 

@@ -610,6 +610,10 @@ int conv0_wgrad_combine(const float* sums, const float* tab, const float* mean, 
                         hipStream_t st);
 
 int dw_parts(int N, int Ho, int Wo, int C, int dtype, int stride);
+// the compile-time channel-chunk width (4, 6, 8) of the tile launches over this shape (W: the
+// input map's width), 0: the run-time-cbv kernels (another width, a span or tile count past 32
+// bits, FSCNN_DW_GENERIC=1); the launch itself also wants its per-channel rows 16-B aligned
+int dw_ct_width(int N, int Ho, int Wo, int W, int C, int dtype, int stride);
 int dw_fwd(const DwArgs& a, int dtype, hipStream_t st);
 int dw_dgrad(const DwBwdArgs& a, int dtype, hipStream_t st);
 int dw_dgrad_parts(int N, int H, int W, int C, int dtype, int stride);  // BnBwdPart records

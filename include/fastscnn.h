@@ -824,6 +824,11 @@ int fscnn_dropout(const void* x, int ldx, int dtype, int N, int H, int W, int C,
  * Both: counters 512 zeroed uint32 (left zero), tsum 32*3*1024 doubles; *in_kernel (nullable): 1
  * when the kernel's last workgroups ran the finish, 0 when it was a launch of its own. */
 int fscnn_dw3x3_parts(int N, int H, int W, int C, int stride, int dtype, int dgrad);
+/* Which depthwise tile kernels this shape's launches take (forward, weight gradient, stride-1
+ * input gradient): the compile-time channel-chunk width 4, 6 or 8, or 0 for the run-time-width,
+ * bounds-checked kernels (any other C, spans past 32 bits, FSCNN_DW_GENERIC=1); -1 on bad
+ * arguments.  Both give the same bits (tests/test_gpu_dw_paths.py). */
+int fscnn_dw3x3_ct_width(int N, int H, int W, int C, int stride, int dtype);
 int fscnn_dw3x3_fwd_train(const void* x, int dtype, int N, int H, int W, int C, int stride,
                           const float* w, const float* in_scale, const float* in_shift, void* z,
                           float* part, unsigned* counters, double* tsum, const float* gamma,
