@@ -14,6 +14,9 @@ Submodules:
   deploy         EndToEndFastSCNN — the deployment model: raw frames in, probabilities / mask out
   bev            BirdEyeView / centerline — calibration, view parameters and the centreline read
                  from the row table of EndToEndFastSCNN.bird_eye
+  path           plan / PathPlanner / VisualLateralErrorController — the steering tail: row table
+                 -> fitted path -> wheel PWM in one launch (EndToEndFastSCNN.steer runs it behind
+                 the bird's-eye tail)
   vis            overlay_mask — the lane / class overlay of a frame and a mask on the device
                  (EndToEndFastSCNN.overlay is the same blend fused behind the backbone)
 """

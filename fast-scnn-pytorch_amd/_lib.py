@@ -32,6 +32,22 @@ class AuxHead(ctypes.Structure):
 
 P_aux_head = ctypes.POINTER(AuxHead)
 
+
+class PathParams(ctypes.Structure):
+    """``fscnn_path_params`` of include/fastscnn.h (the steering tail's law)."""
+    _fields_ = [("degree", c_int), ("num_waypoints", c_int), ("fast", c_int), ("min_width", c_int),
+                ("skip_rows", c_int), ("scan_from_bottom", c_int), ("force_bottom_center", c_int),
+                ("reserved", c_int),
+                ("min_x", c_double), ("min_y", c_double), ("max_y", c_double),
+                ("pixels_per_unit", c_double), ("anchor_x", c_double), ("anchor_y", c_double),
+                ("car_x", c_double), ("car_y", c_double), ("steering_gain", c_double),
+                ("base_pwm", c_double), ("curvature_damping", c_double),
+                ("preview_distance", c_double), ("max_pwm", c_double), ("min_pwm", c_double),
+                ("ema_alpha", c_double)]
+
+
+P_path_params = ctypes.POINTER(PathParams)
+
 # name -> (restype, argtypes)
 SIGNATURES = {
     "fscnn_version": (c_char_p, []),
@@ -90,6 +106,7 @@ SIGNATURES = {
     "fscnn_forward_e2e_bev": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, P_float,
                                       P_float, c_int, c_int, c_int, P_double, c_int, c_int, c_int,
                                       c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "fscnn_path_plan": (c_int, [c_vp, c_int, c_int, P_path_params, c_vp, c_vp, c_vp]),
     "fscnn_overlay_mask": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_int,
                                    P_ubyte, c_vp, c_int, c_float, c_float, c_float, c_vp, c_vp,
                                    c_vp]),

@@ -13,7 +13,9 @@ Restates, without OpenCV, what the reference's consumers do around the lane mask
   ``EndToEndFastSCNN.bird_eye`` (``csrc/bev.hip``) leaves, instead of a Python loop over pixels.
 
 The warp itself and the row scan run on the device; this module is host arithmetic on 3 x 3
-matrices and on ``Hb x 4`` integers.  Path smoothing and PWM control are out of scope.
+matrices and on ``Hb x 4`` integers.  Path smoothing, waypoints and the wheel PWM follow in
+``path`` (``csrc/path.hip``), which reads the same row table on the device;
+``EndToEndFastSCNN.steer`` runs both behind the backbone.
 """
 import numpy as np
 

@@ -611,6 +611,16 @@ int fscnn_forward_e2e_bev(const fscnn_plan* plan, const void* x, int x_dtype, in
                          r, ws, stream);
 }
 
+// ---- steering tail (path.hip) ----------------------------------------------------------------------
+int fscnn_path_plan(const int* rows, int N, int Hb, const fscnn_path_params* p, double* ema_state,
+                    double* out, void* stream) {
+  if (!p) {
+    set_error("fscnn_path_plan: null parameters");
+    return E_INVALID;
+  }
+  return path_plan(rows, N, Hb, *p, ema_state, out, S(stream));
+}
+
 // ---- overlay tail (overlay.hip) --------------------------------------------------------------------
 static int overlay_args(const char* who, const void* frames, int frame_dtype, int channels_last,
                         int N, int h, int w, float frame_weight, float alpha, float gamma,

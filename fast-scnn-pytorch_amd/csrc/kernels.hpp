@@ -4,6 +4,8 @@
 #pragma once
 #include "common.hpp"
 
+struct fscnn_path_params;  // include/fastscnn.h
+
 namespace fscnn {
 
 constexpr int MAX_FOLD = 48;  // (45 BatchNorms with the aux head; the table is a kernel argument)
@@ -809,6 +811,12 @@ int overlay_mask(const OverlayArgs& a, const uint8_t* mask, int Hm, int Wm,
                  const OverlayColors& colors, const uint8_t* palette, int P, hipStream_t st);
 int e2e_overlay(const E2eHeadArgs& h, const OverlayArgs& a, const OverlayColors& colors, int dtype,
                 hipStream_t st);
+// Steering tail (path.hip): row table -> centreline -> QR polynomial fit -> waypoints -> preview
+// point -> EMA -> wheel PWM, one workgroup per frame (include/fastscnn.h: the law, the record).
+// ema_state: device double [N][2] or null; out: device double [N][FSCNN_PATH_REC + 2 * K].
+bool path_plan_ok(int N, int Hb, int degree, int K);
+int path_plan(const int* rows, int N, int Hb, const fscnn_path_params& p, double* ema_state,
+              double* out, hipStream_t st);
 int dropout(const DropArgs& a, int dtype, hipStream_t st);
 // GPU input path: ToTensor + Normalize of uint8 HWC images into NCHW (fp32 / bf16)
 int normalize_u8(const uint8_t* x, int N, int H, int W, const float* mean, const float* std,

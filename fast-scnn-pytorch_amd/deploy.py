@@ -36,6 +36,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from . import bev as _bev
+from . import path as _path
 from .fast_scnn import E_UNSUPPORTED
 
 __all__ = ["EndToEndFastSCNN", "EndToEndPreprocessing"]
@@ -301,6 +302,26 @@ class EndToEndFastSCNN(nn.Module):
                                         return_mask)
         object.__setattr__(self, "_last_fused", fused)
         return mask, rows
+
+    # ---- the steering tail ------------------------------------------------------------------------
+    def steer(self, frames, view_params, controller=None, smooth_method="polynomial", degree=3,
+              num_waypoints=20, min_width=10, fast_mode=True, force_bottom_center=True, scale=255,
+              anchor=None, car_position=None, return_rows=False):
+        """Raw frames -> the wheel commands: ``bird_eye(frames, view_params, scale, min_width,
+        return_mask=False)`` and then ``path.plan`` on its row table, on the same stream, with
+        nothing read back in between (two launches after the backbone on ``bird_eye``'s fused
+        route, three on its ``predict`` + ``fscnn_bev_mask`` route for large views).  Returns the float64
+        record ``[N, path.REC + 2 * num_waypoints]`` on the device (``path.PWM_LEFT`` /
+        ``path.PWM_RIGHT`` and the other offsets of ``path``; ``controller.control_result(i)``
+        gives the reference's dictionary), and the row table too with ``return_rows``.  The
+        planner arguments are ``plan_complete_path``'s, ``controller`` a
+        ``path.VisualLateralErrorController`` whose EMA state stays on the device, one slot per
+        batch index."""
+        _, rows = self.bird_eye(frames, view_params, scale=scale, min_width=max(int(min_width), 1),
+                                return_mask=False)
+        rec = _path.plan(rows, view_params, controller, smooth_method, degree, num_waypoints,
+                         min_width, fast_mode, force_bottom_center, anchor, car_position)
+        return (rec, rows) if return_rows else rec
 
     # ---- the overlay tail -------------------------------------------------------------------------
     def _fused_overlay(self, h, w):

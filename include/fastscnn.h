@@ -283,6 +283,89 @@ int fscnn_forward_e2e_overlay(const fscnn_plan* plan, const void* x, int x_dtype
                               float frame_weight, float alpha, float gamma, unsigned char* out,
                               unsigned char* mask_out, const float* params, float* running,
                               long long* nbt, void* ws, void* stream);
+/* Steering tail of the deployment pipeline: from the row table of the bird's-eye tail to the two
+ * wheel commands, what the reference does on the host with PathPlanner.smooth_path /
+ * generate_waypoints / plan_complete_path / _calculate_path_length
+ * (kuruma/vision/path_planning.py:316-525) and VisualLateralErrorController.compute_wheel_pwm
+ * (kuruma/control/visual_controller.py:72-207, 236-308).  One launch, one workgroup per frame, no
+ * workspace, no atomics; the host reads nothing in between.
+ *
+ * The law, per frame, from rows[Hb][4] (run_start, run_end, count, index_sum); all arithmetic fp64.
+ *   selection  fast != 0 (extract_centerline_fast): the rows y = Hb-1, Hb-1-skip_rows, ...
+ *              (scan_from_bottom != 0) or y = 0, skip_rows, ... whose count >= min_width and > 0;
+ *              pixel px = index_sum div count.  fast == 0 (extract_centerline): every row with
+ *              run_end > run_start and run_end - run_start >= min_width; px = (run_start + run_end)
+ *              div 2; skip_rows and scan_from_bottom are not read.  World point
+ *              (x, y) = (min_x + px / pixels_per_unit, min_y + py / pixels_per_unit).
+ *              plan_complete_path's fast mode passes min_width div 2, skip_rows 3 and
+ *              degree = min(2, degree): those defaults are the caller's (path.py), not the kernel's.
+ *   fit        weighted least squares x = f(y), degree d in 1 .. 3, every centreline point with
+ *              weight 1; with force_bottom_center one more point (anchor_x, anchor_y) of weight 1e6,
+ *              the weight multiplying the row [y^d .. y 1 | x] as in np.polyfit(..., w=).  No
+ *              centreline point: no path (FSCNN_PATH_NO_CENTERLINE; the reference's early return,
+ *              taken even where the anchor alone would be enough points).  Fewer than d + 1 points,
+ *              anchor included: no path (FSCNN_PATH_TOO_FEW).  The system is solved by a QR
+ *              factorisation (Givens rotations, rows in no particular order), never through the
+ *              normal equations.  If a diagonal of the triangular factor is below npoints * 2^-52
+ *              times the largest, the frame has no path (FSCNN_PATH_RANK_DEFICIENT); np.polyfit
+ *              would return the truncated-SVD answer with a RankWarning there, which this law does
+ *              not reproduce.
+ *   waypoints  K values y_i = min_y + i * ((max_y - min_y) / (K - 1)), the last exactly max_y, y_0 =
+ *              min_y when K = 1 (np.linspace); x_i by Horner from the highest coefficient, product
+ *              and sum rounded separately (np.poly1d).  Path length = sum of the K - 1 segment
+ *              lengths sqrt(dx*dx + dy*dy) (summed pairwise, not left to right).
+ *   preview    among the waypoints with y_i < car_y, the one whose |sqrt((x_i - car_x)^2 +
+ *              (y_i - car_y)^2) - preview_distance| is smallest, the first on ties; if none is
+ *              ahead, the waypoint of smallest y, the first on ties (FSCNN_PATH_NONE_AHEAD).
+ *              raw = control_x - car_x; with no path raw = 0.0 exactly and the control point is
+ *              absent.
+ *   EMA        with ema_state: e = raw and state = raw on a slot's first call (flag 0), afterwards
+ *              e = state = ema_alpha * raw + (1 - ema_alpha) * state.  Without: e = raw.
+ *   wheels     steering = steering_gain * e
+ *              dynamic  = min(max(base_pwm / (1 + curvature_damping * |e|), min_pwm), max_pwm)
+ *              left  = min(max(dynamic + steering, -1000), 1000)
+ *              right = min(max(dynamic - steering, -1000), 1000)
+ * Anchor and car position are both the reference's bottom-centre point: image pixel (320, 359, 1)
+ * through view_params['image_to_world_matrix'] in float32 (_get_bottom_center_world_coord,
+ * _get_car_position_world; the pixel is hard-coded there whatever the frame size).  The caller
+ * computes it once on the host and passes it as doubles.
+ *
+ * out: double [N][FSCNN_PATH_REC + 2 * K] per frame, at the offsets below; then the K waypoints
+ * (x_i, y_i).  Absent values (coefficients above d, and with no path every coefficient, the
+ * control point and the waypoints) are NaN; with no path the length is 0 and FSCNN_PATH_NWAY is 0.
+ * ema_state: DEVICE double [N][2] = (state, flag: 0 = not yet initialised), one batch slot per
+ * camera stream, read and updated by the kernel; null = smoothing off.
+ * Limits: K 1 .. 256, degree 1 .. 3, Hb 1 .. 65535, N 1 .. 65535, otherwise -2 and nothing is
+ * launched.  Parameters that are not finite, pixels_per_unit == 0, skip_rows < 1 or min_width < 0:
+ * -1. */
+#define FSCNN_PATH_COEF 0        /* 4 slots: the d + 1 coefficients, highest power first */
+#define FSCNN_PATH_NPOINTS 4     /* centreline points (the anchor not counted) */
+#define FSCNN_PATH_STATUS 5      /* the bits below, as a double */
+#define FSCNN_PATH_LENGTH 6
+#define FSCNN_PATH_CONTROL_X 7
+#define FSCNN_PATH_CONTROL_Y 8
+#define FSCNN_PATH_RAW_ERROR 9   /* raw_lateral_error */
+#define FSCNN_PATH_ERROR 10      /* lateral_error (after the EMA) */
+#define FSCNN_PATH_STEERING 11   /* steering_adjustment */
+#define FSCNN_PATH_DYNAMIC 12    /* dynamic_pwm */
+#define FSCNN_PATH_PWM_LEFT 13
+#define FSCNN_PATH_PWM_RIGHT 14
+#define FSCNN_PATH_NWAY 15       /* number of waypoints: K, or 0 with no path */
+#define FSCNN_PATH_REC 16
+#define FSCNN_PATH_NO_CENTERLINE 1
+#define FSCNN_PATH_TOO_FEW 2
+#define FSCNN_PATH_RANK_DEFICIENT 4
+#define FSCNN_PATH_NONE_AHEAD 8
+typedef struct fscnn_path_params {
+  int degree, num_waypoints;
+  int fast, min_width, skip_rows, scan_from_bottom, force_bottom_center, reserved;
+  double min_x, min_y, max_y, pixels_per_unit;  /* view_bounds, pixels_per_unit */
+  double anchor_x, anchor_y, car_x, car_y;
+  double steering_gain, base_pwm, curvature_damping, preview_distance, max_pwm, min_pwm;
+  double ema_alpha;
+} fscnn_path_params;
+int fscnn_path_plan(const int* rows, int N, int Hb, const fscnn_path_params* p, double* ema_state,
+                    double* out, void* stream);
 
 /* SegmentationMetric counters (utils/metric.py:73-105, batch_pix_accuracy +
  * batch_intersection_union) of n predictions (pred_dtype 0 int64, 1 uint8) against int64 labels,
