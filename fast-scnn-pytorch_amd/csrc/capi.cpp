@@ -228,6 +228,28 @@ struct fscnn_plan {
 
 static hipStream_t S(void* s) { return (hipStream_t)s; }
 
+// What every whole-network entry passes to net_forward / net_backward alike; an entry adds its own
+// outputs and head fields.  out_dtype is the plan's (the two entries that write logits set the
+// caller's); the inference entries pass seed 0, dropout_p 0 and momentum 0.1f.
+static RunArgs forward_args(const Plan& pl, const void* x, int x_dtype, const float* params,
+                            float* running, long long* nbt, void* ws, unsigned long long seed,
+                            float dropout_p, float momentum, void* stream) {
+  RunArgs r{};
+  r.x = x; r.x_dtype = x_dtype; r.out_dtype = pl.dtype;
+  r.P = params; r.R = running; r.NBT = nbt; r.ws = ws;
+  r.seed = seed; r.dropout_p = dropout_p; r.momentum = momentum; r.st = S(stream);
+  return r;
+}
+
+static RunArgs backward_args(const void* x, int x_dtype, const float* params, float* grads,
+                             void* ws, void* bws, unsigned long long seed, float dropout_p,
+                             void* stream) {
+  RunArgs r{};
+  r.x = x; r.x_dtype = x_dtype; r.P = params; r.G = grads; r.ws = ws; r.bws = bws;
+  r.seed = seed; r.dropout_p = dropout_p; r.st = S(stream);
+  return r;
+}
+
 extern "C" {
 
 const char* fscnn_version(void) { return "fastscnn-hip 0.1 (gfx950)"; }
@@ -317,10 +339,9 @@ int fscnn_forward(const fscnn_plan* plan, const void* x, int x_dtype, void* out,
     set_error("fscnn_forward: null argument");
     return E_INVALID;
   }
-  RunArgs r{};
-  r.x = x; r.x_dtype = x_dtype; r.out = out; r.out_dtype = out_dtype;
-  r.P = params; r.R = running; r.NBT = nbt; r.ws = ws;
-  r.seed = seed; r.dropout_p = dropout_p; r.momentum = momentum; r.st = S(stream);
+  RunArgs r = forward_args(plan->plan, x, x_dtype, params, running, nbt, ws, seed, dropout_p,
+                           momentum, stream);
+  r.out = out; r.out_dtype = out_dtype;
   GUARD(net_forward(plan->plan, r));
 }
 
@@ -332,9 +353,8 @@ int fscnn_backward(const fscnn_plan* plan, const void* dout, const void* x, int 
     set_error("fscnn_backward: null argument");
     return E_INVALID;
   }
-  RunArgs r{};
-  r.dout = dout; r.x = x; r.x_dtype = x_dtype; r.P = params; r.G = grads; r.ws = ws; r.bws = bws;
-  r.seed = seed; r.dropout_p = dropout_p; r.st = S(stream);
+  RunArgs r = backward_args(x, x_dtype, params, grads, ws, bws, seed, dropout_p, stream);
+  r.dout = dout;
   GUARD(net_backward(plan->plan, r, stage_from, stage_to));
 }
 
@@ -346,10 +366,9 @@ int fscnn_forward_aux(const fscnn_plan* plan, const void* x, int x_dtype, void* 
     set_error("fscnn_forward_aux: null argument");
     return E_INVALID;
   }
-  RunArgs r{};
-  r.x = x; r.x_dtype = x_dtype; r.out = out; r.aux_out = aux_out; r.out_dtype = out_dtype;
-  r.P = params; r.R = running; r.NBT = nbt; r.ws = ws;
-  r.seed = seed; r.dropout_p = dropout_p; r.momentum = momentum; r.st = S(stream);
+  RunArgs r = forward_args(plan->plan, x, x_dtype, params, running, nbt, ws, seed, dropout_p,
+                           momentum, stream);
+  r.out = out; r.aux_out = aux_out; r.out_dtype = out_dtype;
   GUARD(net_forward(plan->plan, r));
 }
 
@@ -361,9 +380,8 @@ int fscnn_backward_aux(const fscnn_plan* plan, const void* dout, const void* dau
     set_error("fscnn_backward_aux: null argument");
     return E_INVALID;
   }
-  RunArgs r{};
-  r.dout = dout; r.daux = daux; r.x = x; r.x_dtype = x_dtype; r.P = params; r.G = grads;
-  r.ws = ws; r.bws = bws; r.seed = seed; r.dropout_p = dropout_p; r.st = S(stream);
+  RunArgs r = backward_args(x, x_dtype, params, grads, ws, bws, seed, dropout_p, stream);
+  r.dout = dout; r.daux = daux;
   GUARD(net_backward(plan->plan, r, stage_from, stage_to));
 }
 
@@ -382,10 +400,8 @@ int fscnn_predict(const fscnn_plan* plan, const void* x, int x_dtype, void* labe
     set_error("fscnn_predict: label_dtype %d (0 int64, 1 uint8)", label_dtype);
     return E_INVALID;
   }
-  RunArgs r{};
-  r.x = x; r.x_dtype = x_dtype; r.out = nullptr; r.out_dtype = plan->plan.dtype;
+  RunArgs r = forward_args(plan->plan, x, x_dtype, params, running, nbt, ws, 0, 0.f, 0.1f, stream);
   r.labels = labels; r.label_u8 = label_dtype;
-  r.P = params; r.R = running; r.NBT = nbt; r.ws = ws; r.momentum = 0.1f; r.st = S(stream);
   GUARD(net_forward(plan->plan, r));
 }
 
@@ -425,9 +441,7 @@ int fscnn_validate(const fscnn_plan* plan, const void* x, int x_dtype, const lon
               "%dx%d)", pl.net->num_classes, pl.H, pl.W, pl.H3, pl.W3);
     return E_UNSUPPORTED;
   }
-  RunArgs r{};
-  r.x = x; r.x_dtype = x_dtype; r.out = nullptr; r.out_dtype = pl.dtype;
-  r.P = params; r.R = running; r.NBT = nbt; r.ws = ws; r.momentum = 0.1f; r.st = S(stream);
+  RunArgs r = forward_args(pl, x, x_dtype, params, running, nbt, ws, 0, 0.f, 0.1f, stream);
   r.validate = 1; r.target = target; r.ignore_index = ignore_index; r.loss2 = loss;
   r.head = head; r.smooth = smooth; r.dice_weight = dice_weight; r.focal_weight = focal_weight;
   r.alpha = alpha; r.gamma = gamma; r.aux_weight = aux_weight;
@@ -499,7 +513,8 @@ long long fscnn_e2e_ws_bytes(const fscnn_plan* plan) {
 }
 
 // fscnn_forward_e2e and fscnn_forward_e2e_bev: the front end, then the backbone ending in the tail
-// that `r` names.  tail_ok: the tail's geometry check, made before anything is launched.
+// that `r` names (its x is set here).  tail_ok: the tail's geometry check, made before anything
+// is launched.
 static int forward_e2e_run(const char* who, const fscnn_plan* plan, const void* x, int x_dtype,
                            int channels_last, int bgr, int h, int w, const float* mean,
                            const float* std, bool tail_ok, RunArgs& r, void* ws, void* stream) {
@@ -524,8 +539,7 @@ static int forward_e2e_run(const char* who, const fscnn_plan* plan, const void* 
   E2ePreArgs a{};
   if (int rc = e2e_pre_args(x, channels_last, bgr, pl.N, h, w, pl.H, mean, std, xin, a)) return rc;
   if (int rc = e2e_pre(a, x_dtype, pl.dtype, S(stream))) return rc;
-  r.x = xin; r.x_dtype = pl.dtype; r.out = nullptr; r.out_dtype = pl.dtype;
-  r.ws = ws; r.momentum = 0.1f; r.st = S(stream);
+  r.x = xin;
   GUARD(net_forward(plan->plan, r));
 }
 
@@ -543,8 +557,7 @@ int fscnn_forward_e2e(const fscnn_plan* plan, const void* x, int x_dtype, int ch
     return E_INVALID;
   }
   const Plan& pl = plan->plan;
-  RunArgs r{};
-  r.P = params; r.R = running; r.NBT = nbt;
+  RunArgs r = forward_args(pl, nullptr, pl.dtype, params, running, nbt, ws, 0, 0.f, 0.1f, stream);
   r.e2e_ho = h_out; r.e2e_wo = w_out; r.e2e_softmax = softmax != 0; r.e2e_probs = probs;
   r.e2e_pdtype = probs_dtype; r.e2e_labels = labels; r.e2e_scale = label_scale;
   return forward_e2e_run("fscnn_forward_e2e", plan, x, x_dtype, channels_last, bgr, h, w, mean, std,
@@ -600,8 +613,7 @@ int fscnn_forward_e2e_bev(const fscnn_plan* plan, const void* x, int x_dtype, in
       return E_INVALID;
     }
   const Plan& pl = plan->plan;
-  RunArgs r{};
-  r.P = params; r.R = running; r.NBT = nbt;
+  RunArgs r = forward_args(pl, nullptr, pl.dtype, params, running, nbt, ws, 0, 0.f, 0.1f, stream);
   r.e2e_ho = h_out; r.e2e_wo = w_out; r.e2e_scale = label_scale;
   r.bev_hb = Hb; r.bev_wb = Wb; r.bev_min_width = min_width; r.bev_mask = bev; r.bev_rows = rows;
   for (int i = 0; i < 9; ++i) r.bev_m[i] = m[i];
@@ -700,7 +712,7 @@ int fscnn_forward_e2e_overlay(const fscnn_plan* plan, const void* x, int x_dtype
     return E_INVALID;
   }
   const Plan& pl = plan->plan;
-  RunArgs r{};
+  RunArgs r = forward_args(pl, nullptr, pl.dtype, params, running, nbt, ws, 0, 0.f, 0.1f, stream);
   if (int rc = overlay_args("fscnn_forward_e2e_overlay", x, x_dtype, channels_last, pl.N, h, w,
                             frame_weight, alpha, gamma, out, mask_out, r.ov))
     return rc;
@@ -717,7 +729,6 @@ int fscnn_forward_e2e_overlay(const fscnn_plan* plan, const void* x, int x_dtype
   if (int rc = overlay_colors("fscnn_forward_e2e_overlay", colors, pl.net->num_classes,
                               class_mask, r.ov_colors))
     return rc;
-  r.P = params; r.R = running; r.NBT = nbt;
   r.e2e_ho = h_out; r.e2e_wo = w_out; r.e2e_scale = label_scale;
   return forward_e2e_run("fscnn_forward_e2e_overlay", plan, x, x_dtype, channels_last, bgr, h, w,
                          mean, std, e2e_overlay_ok(pl.N, pl.net->num_classes, pl.H3, pl.W3, pl.H,
@@ -870,10 +881,8 @@ int fscnn_forward_loss(const fscnn_plan* plan, const void* x, int x_dtype, const
     set_error("fscnn_forward_loss: null argument");
     return E_INVALID;
   }
-  RunArgs r{};
-  r.x = x; r.x_dtype = x_dtype; r.out = nullptr; r.out_dtype = plan->plan.dtype;
-  r.P = params; r.R = running; r.NBT = nbt; r.ws = ws;
-  r.seed = seed; r.dropout_p = dropout_p; r.momentum = momentum; r.st = S(stream);
+  RunArgs r = forward_args(plan->plan, x, x_dtype, params, running, nbt, ws, seed, dropout_p,
+                           momentum, stream);
   r.target = target; r.ignore_index = ignore_index; r.loss2 = loss2;
   GUARD(net_forward(plan->plan, r));
 }
@@ -886,10 +895,8 @@ int fscnn_backward_loss(const fscnn_plan* plan, const float* grad_loss, const fl
     set_error("fscnn_backward_loss: null argument");
     return E_INVALID;
   }
-  RunArgs r{};
+  RunArgs r = backward_args(x, x_dtype, params, grads, ws, bws, seed, dropout_p, stream);
   r.gloss = grad_loss; r.loss2 = const_cast<float*>(loss2);
-  r.x = x; r.x_dtype = x_dtype; r.P = params; r.G = grads; r.ws = ws; r.bws = bws;
-  r.seed = seed; r.dropout_p = dropout_p; r.st = S(stream);
   GUARD(net_backward(plan->plan, r, stage_from, stage_to));
 }
 
@@ -912,10 +919,8 @@ int fscnn_forward_loss_dice(const fscnn_plan* plan, const void* x, int x_dtype,
     set_error("fscnn_forward_loss_dice: null argument");
     return E_INVALID;
   }
-  RunArgs r{};
-  r.x = x; r.x_dtype = x_dtype; r.out = nullptr; r.out_dtype = plan->plan.dtype;
-  r.P = params; r.R = running; r.NBT = nbt; r.ws = ws;
-  r.seed = seed; r.dropout_p = dropout_p; r.momentum = momentum; r.st = S(stream);
+  RunArgs r = forward_args(plan->plan, x, x_dtype, params, running, nbt, ws, seed, dropout_p,
+                           momentum, stream);
   r.target = target; r.ignore_index = -1; r.loss2 = loss_out;
   r.head = HEAD_DICE; r.smooth = smooth; r.dice_weight = dice_weight;
   r.focal_weight = focal_weight; r.alpha = alpha; r.gamma = gamma;
@@ -936,12 +941,10 @@ int fscnn_backward_loss_dice(const fscnn_plan* plan, const float* grad_loss, con
     set_error("backward_loss: the fused loss head covers the main output only (aux net)");
     return E_UNSUPPORTED;
   }
-  RunArgs r{};
+  RunArgs r = backward_args(x, x_dtype, params, grads, ws, bws, seed, dropout_p, stream);
   r.gloss = grad_loss;
   r.head = HEAD_DICE; r.smooth = smooth; r.dice_weight = dice_weight;
   r.focal_weight = focal_weight; r.head_ws = head_ws; r.dice_stats = const_cast<double*>(stats);
-  r.x = x; r.x_dtype = x_dtype; r.P = params; r.G = grads; r.ws = ws; r.bws = bws;
-  r.seed = seed; r.dropout_p = dropout_p; r.st = S(stream);
   GUARD(net_backward(plan->plan, r, stage_from, stage_to));
 }
 
@@ -971,10 +974,8 @@ int fscnn_forward_loss_ohem(const fscnn_plan* plan, const void* x, int x_dtype,
               plan->plan.net->num_classes);
     return E_UNSUPPORTED;
   }
-  RunArgs r{};
-  r.x = x; r.x_dtype = x_dtype; r.out = nullptr; r.out_dtype = plan->plan.dtype;
-  r.P = params; r.R = running; r.NBT = nbt; r.ws = ws;
-  r.seed = seed; r.dropout_p = dropout_p; r.momentum = momentum; r.st = S(stream);
+  RunArgs r = forward_args(plan->plan, x, x_dtype, params, running, nbt, ws, seed, dropout_p,
+                           momentum, stream);
   r.target = target; r.ignore_index = ignore_index; r.loss2 = loss2;
   r.head = HEAD_OHEM; r.ohem_thresh = thresh; r.ohem_min_kept = min_kept;
   r.ohem_weight = weight; r.ohem_prob = prob; r.ohem_thr = thr; r.ohem_counts = counts;
@@ -1055,11 +1056,9 @@ int fscnn_forward_loss_aux(const fscnn_plan* plan, const void* x, int x_dtype,
     set_error("fscnn_forward_loss_aux: null argument");
     return E_INVALID;
   }
-  RunArgs r{};
+  RunArgs r = forward_args(plan->plan, x, x_dtype, params, running, nbt, ws, seed, dropout_p,
+                           momentum, stream);
   if (int rc = aux_head_args("fscnn_forward_loss_aux", plan, h, r)) return rc;
-  r.x = x; r.x_dtype = x_dtype; r.out = nullptr; r.out_dtype = plan->plan.dtype;
-  r.P = params; r.R = running; r.NBT = nbt; r.ws = ws;
-  r.seed = seed; r.dropout_p = dropout_p; r.momentum = momentum; r.st = S(stream);
   r.target = target; r.loss3 = loss_out; r.head_ws = head_ws;
   GUARD(net_forward(plan->plan, r));
 }
@@ -1073,16 +1072,13 @@ int fscnn_backward_loss_aux(const fscnn_plan* plan, const float* grad_loss,
     set_error("fscnn_backward_loss_aux: null argument");
     return E_INVALID;
   }
-  RunArgs r{};
+  RunArgs r = backward_args(x, x_dtype, params, grads, ws, bws, seed, dropout_p, stream);
   if (int rc = aux_head_args("fscnn_backward_loss_aux", plan, h, r)) return rc;
   if (dx && h->head == HEAD_DICE) {
     set_error("fscnn_backward_loss_aux: the Dice head does not form the input gradient");
     return E_INVALID;
   }
-  r.gloss = grad_loss; r.head_ws = head_ws;
-  r.x = x; r.x_dtype = x_dtype; r.dx = dx; r.dx_dtype = dx_dtype;
-  r.P = params; r.G = grads; r.ws = ws; r.bws = bws;
-  r.seed = seed; r.dropout_p = dropout_p; r.st = S(stream);
+  r.gloss = grad_loss; r.head_ws = head_ws; r.dx = dx; r.dx_dtype = dx_dtype;
   GUARD(net_backward(plan->plan, r, stage_from, stage_to));
 }
 
@@ -1096,11 +1092,9 @@ int fscnn_backward_dx(const fscnn_plan* plan, const void* dout, const void* daux
     set_error("fscnn_backward_dx: null argument (exactly one of dout / grad_loss + loss2)");
     return E_INVALID;
   }
-  RunArgs r{};
+  RunArgs r = backward_args(x, x_dtype, params, grads, ws, bws, seed, dropout_p, stream);
   r.dout = dout; r.daux = daux; r.gloss = grad_loss; r.loss2 = const_cast<float*>(loss2);
-  r.x = x; r.x_dtype = x_dtype; r.dx = dx; r.dx_dtype = dx_dtype;
-  r.P = params; r.G = grads; r.ws = ws; r.bws = bws;
-  r.seed = seed; r.dropout_p = dropout_p; r.st = S(stream);
+  r.dx = dx; r.dx_dtype = dx_dtype;
   GUARD(net_backward(plan->plan, r, stage_from, stage_to));
 }
 

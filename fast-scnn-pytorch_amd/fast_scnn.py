@@ -16,6 +16,7 @@ are views of one flat gradient arena, so the fused SGD and the RCCL all-reduce e
 single buffer.  The submodules are parameter containers only: the whole network runs as one
 native forward and one staged native backward.  CPU tensors raise — there is no fallback.
 """
+import collections
 import os
 import threading
 
@@ -378,69 +379,46 @@ def _aux_head_spec(criterion):
     return spec
 
 
-class _FastSCNNAuxLossFunction(torch.autograd.Function):
-    """Fused train step heads of an aux model: loss = L(out) + aux_weight * L(aux_out), both at
-    low resolution.  ``spec``: an ``_aux_head_spec`` tuple (OHEM: its weights on the device).  The
-    heads' state travels to the backward in one buffer, ``head_ws``; the returned loss is a tensor
-    of its own, which the backward never reads (the caller may scale it in place)."""
-
-    @staticmethod
-    def forward(ctx, x, target, spec, model, ar, *params):
-        if spec[0] == "dice" and ctx.needs_input_grad[0]:
-            raise RuntimeError("forward_loss_aux: the fused Dice head does not form the input "
-                               "image's gradient; use criterion(model(x), target)")
-        loss3, ws, seed, dt, xc, head, head_ws = model._run_forward_loss_aux(x, target, spec, ar)
-        ctx.model, ctx.ar = model, ar
-        ctx.ws, ctx.seed, ctx.dt, ctx.aux = ws, seed, dt, (head, head_ws, spec)
-        ctx.x_dtype = x.dtype
-        ctx.save_for_backward(xc, *params)
-        model._last_loss_terms = loss3[1:]
-        out = torch.empty((), dtype=loss3.dtype, device=loss3.device)
-        return out.set_(loss3.untyped_storage(), loss3.storage_offset(), (), ())
-
-    @staticmethod
-    def backward(ctx, gloss):
-        x = ctx.saved_tensors[0]
-        g = gloss.to(torch.float32).reshape(1).contiguous()
-        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        grads = ctx.model._run_backward(None, x, ctx.ws, ctx.seed, ctx.dt, ctx.ar, gloss=g,
-                                        dx=dx, aux_head=ctx.aux)
-        ctx.ws = ctx.ar = ctx.aux = None
-        if dx is not None and dx.dtype != ctx.x_dtype:
-            dx = dx.to(ctx.x_dtype)
-        return (dx, None, None, None, None) + tuple(grads)
+# what a native forward's prologue hands its entry (FastSCNN._prologue): the plan, the buffers and
+# converted tensors, and the C call's common arguments -- src = (plan, x, x_dtype) leads, mem =
+# (P, R, NBT, ws) and end = ([seed, p, momentum,] stream) close it
+_Call = collections.namedtuple("_Call", "plan fw ws dt x target N H W dev p seed ar src mem end")
+# what the backward needs of a fused loss head: its C backward entry, the entry's arguments
+# between grad_loss and x, the head's own workspace or None, and what those point to (kept alive)
+_Head = collections.namedtuple("_Head", "entry lead head_ws keep")
+_ONE_SAMPLE = ("Expected more than 1 value per channel when training, got input size "
+               "torch.Size([1, 32, 1, 1])")
 
 
 class _FastSCNNLossFunction(torch.autograd.Function):
-    """Fused train step head: loss = criterion(upsample(logits_lowres), target) at low
-    resolution.  ``head`` is the CE head's ignore_index (an int), a Dice ``_head_spec`` tuple or
-    an ``_ohem_spec`` tuple (its weights on the device); the Dice head's coefficient planes
-    (``head_ws``) and sums (``stats``) travel to the backward in ``ctx.dice``.  The OHEM head
-    leaves ``loss2`` and the low-res gradient planes in the CE head's format: same backward."""
+    """Fused train step heads: loss = criterion(upsample(logits_lowres), target) at low
+    resolution, for an aux model L(out) + aux_weight * L(aux_out).  ``entry`` names the model's
+    method; ``spec`` is its criterion tuple (``_head_spec``, ``_ohem_spec`` or ``_aux_head_spec``;
+    OHEM weights on the device), whose first item picks the forward.  The forward's ``_Head``
+    travels to the backward.  The returned loss shares the storage of the head's loss tensor."""
 
     @staticmethod
-    def forward(ctx, x, target, head, model, ar, *params):
-        ctx.dice = None
-        if isinstance(head, tuple) and head[0] == "ohem":
-            loss2, ws, seed, dt, xc = model._run_forward_loss_ohem(x, target, head, ar)
-        elif isinstance(head, tuple):
-            if ctx.needs_input_grad[0]:
-                raise RuntimeError("forward_loss: the fused Dice head does not form the input "
-                                   "image's gradient; use criterion(model(x), target)")
-            loss2, ws, seed, dt, xc, head_ws, stats = model._run_forward_loss_dice(
-                x, target, head, ar)
-            ctx.dice = (head, head_ws, stats)
-        else:
-            loss2, ws, seed, dt, xc = model._run_forward_loss(x, target, head, ar)
+    def forward(ctx, x, target, entry, spec, model, ar, *params):
+        if spec[0] == "dice" and ctx.needs_input_grad[0]:
+            raise RuntimeError("%s: the fused Dice head does not form the input image's "
+                               "gradient; use criterion(model(x), target)" % entry)
+        aux = entry == "forward_loss_aux"
+        run = model._run_forward_loss_aux if aux else {
+            "ce": model._run_forward_loss, "dice": model._run_forward_loss_dice,
+            "ohem": model._run_forward_loss_ohem}[spec[0]]
+        loss, c, ctx.head = run(x, target, spec, ar)
         ctx.model, ctx.ar = model, ar
-        ctx.ws, ctx.seed, ctx.dt, ctx.loss2 = ws, seed, dt, loss2
+        ctx.ws, ctx.seed, ctx.dt = c.ws, c.seed, c.dt
         ctx.x_dtype = x.dtype
-        ctx.save_for_backward(xc, *params)
-        # the mean of the (mean, count) pair the head wrote, as a tensor sharing its storage but
-        # not an autograd view (a view created here would refuse the in-place ops the reference's
-        # loss tensor allows: loss /= accum_steps); the backward reads only the count, loss2[1]
-        out = torch.empty((), dtype=loss2.dtype, device=loss2.device)
-        return out.set_(loss2.untyped_storage(), loss2.storage_offset(), (), ())
+        ctx.save_for_backward(c.x, *params)
+        if aux:
+            model._last_loss_terms = loss[1:]
+        # the first element of what the head wrote (CE / OHEM: the (mean, count) pair), as a
+        # tensor sharing its storage but not an autograd view (a view created here would refuse
+        # the in-place ops the reference's loss tensor allows: loss /= accum_steps); the backward
+        # never reads it
+        out = torch.empty((), dtype=loss.dtype, device=loss.device)
+        return out.set_(loss.untyped_storage(), loss.storage_offset(), (), ())
 
     @staticmethod
     def backward(ctx, gloss):
@@ -448,11 +426,11 @@ class _FastSCNNLossFunction(torch.autograd.Function):
         g = gloss.to(torch.float32).reshape(1).contiguous()
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         grads = ctx.model._run_backward(None, x, ctx.ws, ctx.seed, ctx.dt, ctx.ar, gloss=g,
-                                        loss2=ctx.loss2, dx=dx, dice=ctx.dice)
-        ctx.ws = ctx.ar = ctx.dice = None
+                                        dx=dx, head=ctx.head)
+        ctx.ws = ctx.ar = ctx.head = None
         if dx is not None and dx.dtype != ctx.x_dtype:
             dx = dx.to(ctx.x_dtype)
-        return (dx, None, None, None, None) + tuple(grads)
+        return (dx, None, None, None, None, None) + tuple(grads)
 
 
 class FastSCNN(nn.Module):
@@ -647,59 +625,100 @@ class FastSCNN(nn.Module):
     def _dropout_p(self):
         return float(self.classifier.conv[0].p)
 
-    def _run_forward(self, x, mode, ar=None, dt=None):
-        """One native forward; mode: MODE_EVAL (0), MODE_TRAIN (1), MODE_EVAL_GRAD (2); dt: the
-        arithmetic (default: _compute_dtype)."""
-        train = mode == MODE_TRAIN
-        if x.dim() != 4 or x.shape[1] != 3:
+    def _prologue(self, who, x, mode, ar=None, target=None, check=None, dt=None, refuse=None,
+                  checks="", scalars=True):
+        """What every native forward does before its C call, as a ``_Call`` record.
+
+        ``who``: the entry's name (messages); ``mode``: the plan mode; ``ar``: the arenas
+        (default: ``_exec_arena``); ``target``: the label map of the entries that take one, cast
+        to dense int64; ``check``: its ``loss.CHECK_TARGETS`` law, ``("ce", ignore_index)`` or
+        ``("dice",)``; ``dt``: the arithmetic (default: ``_compute_dtype``); ``scalars``: whether
+        the C entry takes seed, dropout p and BN momentum.  ``checks`` names the refusals of the
+        entry, which come in this order: ``dim`` and ``cuda`` (the image), ``tensors`` (image and
+        target on the device), ``refuse`` (a head's own refusal, a message or None), ``arena``,
+        ``shape`` (of the target) and ``size``.  A train-mode batch of one raises ``ValueError``
+        like the reference's PPM BatchNorm (SURVEY §0 trap 5).  The dropout seed is one draw
+        from the global CPU generator per train-mode forward with p > 0 (``_dropout_seed``
+        pins it: oracle parity in the tests)."""
+        checks, train = checks.split(), mode == MODE_TRAIN
+        if "dim" in checks and (x.dim() != 4 or x.shape[1] != 3):
             raise RuntimeError("FastSCNN: expected input [N, 3, H, W], got %s" % (tuple(x.shape),))
-        if not x.is_cuda:
-            raise RuntimeError("FastSCNN: the HIP path needs a ROCm device tensor (got %s); "
-                               "move the model and input to 'cuda'" % (x.device,))
+        if "cuda" in checks and not x.is_cuda:
+            if who == "forward":
+                raise RuntimeError("FastSCNN: the HIP path needs a ROCm device tensor (got %s); "
+                                   "move the model and input to 'cuda'" % (x.device,))
+            raise RuntimeError("FastSCNN.%s: the HIP path needs a ROCm device tensor" % who)
+        if "tensors" in checks and not (x.is_cuda and target.is_cuda):
+            raise RuntimeError("FastSCNN.%s: the HIP path needs ROCm device tensors" % who)
+        if refuse is not None:
+            raise RuntimeError(refuse)
         nat = self.native()
         if ar is None:
             ar = self._exec_arena(x.device)
-        if ar["P"].device != x.device:
+        if "arena" in checks and ar["P"].device != x.device:
             raise RuntimeError("FastSCNN: input on %s but parameters on %s"
                                % (x.device, ar["P"].device))
         N, _, H, W = x.shape
-        if H < 32 or W < 32:
+        if "shape" in checks and tuple(target.shape) != (N, H, W):
+            raise RuntimeError("%s: target %s does not match input %s"
+                               % (who, tuple(target.shape), tuple(x.shape)))
+        if "size" in checks and (H < 32 or W < 32):
             raise RuntimeError("FastSCNN: input %dx%d too small (needs >= 32x32)" % (H, W))
+        one = train and N < 2
+        if one and target is not None:  # (the loss entries refuse before they look at the dtype)
+            raise ValueError(_ONE_SAMPLE)
         if dt is None:
             dt = self._compute_dtype(x, train)
         x = self._input(x)
-        if train and N < 2:
-            # the reference raises from the PPM 1x1 BatchNorm in train mode (SURVEY §0 trap 5)
-            raise ValueError("Expected more than 1 value per channel when training, got input "
-                             "size torch.Size([1, 32, 1, 1])")
-        plan, fw, _ = nat.plan(N, H, W, _lib.dtype_code(dt), mode, x.device)
-        ws = torch.empty(max(fw, 1), dtype=torch.uint8, device=x.device)
-        out_dt = dt  # (autocast: the reference's final F.interpolate returns fp16 logits)
-        out = torch.empty((N, self.num_classes, H, W), dtype=out_dt, device=x.device)
-        aux_out = torch.empty_like(out) if self.aux else None
+        if one:
+            raise ValueError(_ONE_SAMPLE)
+        if target is not None:
+            target = target.to(torch.int64).contiguous()
+            from . import loss as _loss
+            if _loss.CHECK_TARGETS and check[0] == "dice":  # no ignore_index in Dice
+                bad = (target < 0) | (target >= self.num_classes)
+                if bool(bad.any()):
+                    raise IndexError("Target %d is out of bounds." % int(target[bad].flatten()[0]))
+            elif _loss.CHECK_TARGETS:
+                _loss.check_targets(target, self.num_classes, check[1])
+        dev = x.device
+        plan, fw, _ = nat.plan(N, H, W, _lib.dtype_code(dt), mode, dev)
+        ws = torch.empty(max(fw, 1), dtype=torch.uint8, device=dev)
         p = self._dropout_p() if train else 0.0
         seed = 0
         if train and p > 0:
-            fixed = getattr(self, "_dropout_seed", None)  # tests pin the mask (oracle parity)
+            fixed = getattr(self, "_dropout_seed", None)
             seed = int(fixed) if fixed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
-        rest = (_lib.dtype_code(dt), _lib.ptr(ar["P"]), _lib.ptr(ar["R"]), _lib.ptr(ar["NBT"]),
-                _lib.ptr(ws), _lib.c_ull(seed), _lib.c_float(p), _lib.c_float(self._momentum()),
-                _lib.stream_ptr(x.device))
-        with torch.cuda.device(x.device):
-            if self.aux:  # models/fast_scnn.py:42-45
-                _lib.call("fscnn_forward_aux", plan, _lib.ptr(x), _lib.dtype_code(x.dtype),
-                          _lib.ptr(out), _lib.ptr(aux_out), _lib.dtype_code(out_dt), *rest[1:])
-            else:
-                _lib.call("fscnn_forward", plan, _lib.ptr(x), _lib.dtype_code(x.dtype),
-                          _lib.ptr(out), _lib.dtype_code(out_dt), *rest[1:])
+        end = (_lib.stream_ptr(dev),)
+        if scalars:
+            end = (_lib.c_ull(seed), _lib.c_float(p), _lib.c_float(self._momentum())) + end
+        return _Call(plan, fw, ws, dt, x, target, N, H, W, dev, p, seed, ar,
+                     (plan, _lib.ptr(x), _lib.dtype_code(x.dtype)),
+                     (_lib.ptr(ar["P"]), _lib.ptr(ar["R"]), _lib.ptr(ar["NBT"]), _lib.ptr(ws)), end)
+
+    def _epilogue(self, c, train=True, **debug):
+        """After the C call of a forward whose prologue gave ``c``; ``debug``: the entry's extra
+        ``_debug`` keys."""
         if train:
-            self._writeback(ar)
+            self._writeback(c.ar)
             # the running statistics changed: an eval-mode graph recorded before this forward
             # must not backpropagate through them (_FastSCNNFunction.backward checks)
-            torch.autograd.graph.increment_version(ar["R"])
+            torch.autograd.graph.increment_version(c.ar["R"])
         if getattr(self, "_keep_ws", False):
-            self._debug = {"plan": plan, "ws": ws, "dt": dt}
-        return ((out, aux_out) if self.aux else (out,)), ws, seed, dt, x
+            self._debug = dict(plan=c.plan, ws=c.ws, dt=c.dt, **debug)
+
+    def _run_forward(self, x, mode, ar=None, dt=None):
+        """One native forward; mode: MODE_EVAL (0), MODE_TRAIN (1), MODE_EVAL_GRAD (2); dt: the
+        arithmetic (default: _compute_dtype)."""
+        c = self._prologue("forward", x, mode, ar, dt=dt, checks="dim cuda arena size")
+        # (autocast: the reference's final F.interpolate returns fp16 logits)
+        out = torch.empty((c.N, self.num_classes, c.H, c.W), dtype=c.dt, device=c.dev)
+        outs = (out, torch.empty_like(out)) if self.aux else (out,)  # models/fast_scnn.py:42-45
+        with torch.cuda.device(c.dev):
+            _lib.call("fscnn_forward_aux" if self.aux else "fscnn_forward", *c.src,
+                      *[_lib.ptr(o) for o in outs], _lib.dtype_code(c.dt), *c.mem, *c.end)
+        self._epilogue(c, train=mode == MODE_TRAIN)
+        return outs, c.ws, c.seed, c.dt, c.x
 
     def predict(self, x, dtype=torch.int64):
         """``torch.argmax(self(x)[0], 1)`` of an eval-mode model (eval.py:43-45, demo.py:43-48)
@@ -709,27 +728,12 @@ class FastSCNN(nn.Module):
             raise RuntimeError("predict is the inference path; call model.eval() first")
         if dtype not in (torch.int64, torch.uint8):
             raise RuntimeError("predict: labels are int64 or uint8, not %s" % (dtype,))
-        if x.dim() != 4 or x.shape[1] != 3:
-            raise RuntimeError("FastSCNN: expected input [N, 3, H, W], got %s" % (tuple(x.shape),))
-        if not x.is_cuda:
-            raise RuntimeError("FastSCNN.predict: the HIP path needs a ROCm device tensor")
-        nat = self.native()
-        ar = self._exec_arena(x.device)
-        N, _, H, W = x.shape
-        if H < 32 or W < 32:
-            raise RuntimeError("FastSCNN: input %dx%d too small (needs >= 32x32)" % (H, W))
-        dt = self._compute_dtype(x, False)
-        x = self._input(x)
-        plan, fw, _ = nat.plan(N, H, W, _lib.dtype_code(dt), False, x.device)
-        ws = torch.empty(max(fw, 1), dtype=torch.uint8, device=x.device)
-        labels = torch.empty((N, H, W), dtype=dtype, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.call("fscnn_predict", plan, _lib.ptr(x), _lib.dtype_code(x.dtype),
-                      _lib.ptr(labels), 1 if dtype == torch.uint8 else 0, _lib.ptr(ar["P"]),
-                      _lib.ptr(ar["R"]), _lib.ptr(ar["NBT"]), _lib.ptr(ws),
-                      _lib.stream_ptr(x.device))
-        if getattr(self, "_keep_ws", False):
-            self._debug = {"plan": plan, "ws": ws, "dt": dt}
+        c = self._prologue("predict", x, MODE_EVAL, checks="dim cuda size", scalars=False)
+        labels = torch.empty((c.N, c.H, c.W), dtype=dtype, device=c.dev)
+        with torch.cuda.device(c.dev):
+            _lib.call("fscnn_predict", *c.src, _lib.ptr(labels), 1 if dtype == torch.uint8 else 0,
+                      *c.mem, *c.end)
+        self._epilogue(c, train=False)
         return labels
 
     def validate(self, x, target, criterion=None, metric=None, ignore_index=-1):
@@ -781,50 +785,30 @@ class FastSCNN(nn.Module):
 
     def _validate_fused(self, x, target, criterion, spec, metric):
         """The fused route of ``validate``; None when the library does not take the geometry."""
-        nat = self.native()
-        ar = self._exec_arena(x.device)
-        N, _, H, W = x.shape
-        if H < 32 or W < 32:
-            raise RuntimeError("FastSCNN: input %dx%d too small (needs >= 32x32)" % (H, W))
-        dt = self._compute_dtype(x, False)
-        x = self._input(x)
-        target = target.to(torch.int64).contiguous()
-        from . import loss as _loss
         dice = spec[0] == "dice"
-        if _loss.CHECK_TARGETS:
-            if dice:  # no ignore_index in Dice (forward_loss's check)
-                bad = (target < 0) | (target >= self.num_classes)
-                if bool(bad.any()):
-                    raise IndexError("Target %d is out of bounds." % int(target[bad].flatten()[0]))
-            else:
-                _loss.check_targets(target, self.num_classes, spec[1])
+        c = self._prologue("validate", x, MODE_EVAL, None, target, checks="size", check=spec,
+                           scalars=False)
         ignore = 0 if dice else spec[1]
-        smooth, dw, fw_, alpha, gamma = spec[1:] if dice else (1e-6, 1.0, 0.0, 0.5, 2.0)
+        coef = spec[1:] if dice else (1e-6, 1.0, 0.0, 0.5, 2.0)  # smooth, dice_weight, ...
         aux_w = 0.0
         if self.aux and criterion is not None and getattr(criterion, "aux", False):
             aux_w = float(criterion.aux_weight)
-        plan, fw, _ = nat.plan(N, H, W, _lib.dtype_code(dt), False, x.device)
         lib = _lib.load()
-        hb = int(lib.fscnn_validate_ws_bytes(plan))
+        hb = int(lib.fscnn_validate_ws_bytes(c.plan))
         if hb < 0:
             _lib.check(hb, "fscnn_validate_ws_bytes")
-        ws = torch.empty(max(fw, 1), dtype=torch.uint8, device=x.device)
-        head_ws = torch.empty(max(hb, 1), dtype=torch.uint8, device=x.device)
-        loss = torch.empty(1, dtype=torch.float32, device=x.device)
-        counts = metric.device_counts(x.device) if metric is not None else None
-        with torch.cuda.device(x.device):
-            rc = lib.fscnn_validate(plan, _lib.ptr(x), _lib.dtype_code(x.dtype), _lib.ptr(target),
-                                    1 if dice else 0, int(ignore), _lib.c_float(smooth),
-                                    _lib.c_float(dw), _lib.c_float(fw_), _lib.c_float(alpha),
-                                    _lib.c_float(gamma), _lib.c_float(aux_w), _lib.ptr(loss),
-                                    _lib.ptr(counts), _lib.ptr(ar["P"]), _lib.ptr(ar["R"]),
-                                    _lib.ptr(ar["NBT"]), _lib.ptr(ws), _lib.ptr(head_ws),
-                                    _lib.stream_ptr(x.device))
+        head_ws = torch.empty(max(hb, 1), dtype=torch.uint8, device=c.dev)
+        loss = torch.empty(1, dtype=torch.float32, device=c.dev)
+        counts = metric.device_counts(c.dev) if metric is not None else None
+        with torch.cuda.device(c.dev):
+            rc = lib.fscnn_validate(*c.src, _lib.ptr(c.target), 1 if dice else 0, int(ignore),
+                                    *[_lib.c_float(v) for v in coef], _lib.c_float(aux_w),
+                                    _lib.ptr(loss), _lib.ptr(counts), *c.mem, _lib.ptr(head_ws),
+                                    *c.end)
         if rc == E_UNSUPPORTED:  # nothing was launched: the geometry check comes first
             return None
         _lib.check(rc, "fscnn_validate")
-        if getattr(self, "_keep_ws", False):
-            self._debug = {"plan": plan, "ws": ws, "dt": dt}
+        self._epilogue(c, train=False)
         return loss.reshape(())
 
     def _validate_unfused(self, x, target, criterion, metric, ignore_index):
@@ -860,99 +844,48 @@ class FastSCNN(nn.Module):
         flat = base[off.value:off.value + n * esz].view(dt)
         return flat.as_strided((rows.value, cols.value), (ld.value, 1))
 
-    def _run_forward_loss(self, x, target, ignore_index, ar):
+    def _main_output_only(self, who, criterion):
         if self.aux:
-            raise RuntimeError("forward_loss: the fused loss head covers the main output only; "
-                               "with aux=True use forward_loss_aux(x, target, criterion), or "
-                               "MixSoftmaxCrossEntropyLoss(aux=True)(model(x), target)")
-        if not x.is_cuda or not target.is_cuda:
-            raise RuntimeError("FastSCNN.forward_loss: the HIP path needs ROCm device tensors")
-        nat = self.native()
-        N, _, H, W = x.shape
-        if tuple(target.shape) != (N, H, W):
-            raise RuntimeError("forward_loss: target %s does not match input %s"
-                               % (tuple(target.shape), tuple(x.shape)))
-        if N < 2:
-            raise ValueError("Expected more than 1 value per channel when training, got input "
-                             "size torch.Size([1, 32, 1, 1])")
-        dt = self._compute_dtype(x, True)
-        x = self._input(x)
-        target = target.to(torch.int64).contiguous()
-        from . import loss as _loss
-        if _loss.CHECK_TARGETS:
-            _loss.check_targets(target, self.num_classes, ignore_index)
-        plan, fw, _ = nat.plan(N, H, W, _lib.dtype_code(dt), True, x.device)
-        ws = torch.empty(max(fw, 1), dtype=torch.uint8, device=x.device)
-        loss2 = torch.empty(2, dtype=torch.float32, device=x.device)
-        p = self._dropout_p()
-        seed = 0
-        if p > 0:
-            fixed = getattr(self, "_dropout_seed", None)
-            seed = int(fixed) if fixed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
-        with torch.cuda.device(x.device):
-            _lib.call("fscnn_forward_loss", plan, _lib.ptr(x), _lib.dtype_code(x.dtype),
-                      _lib.ptr(target), int(ignore_index), _lib.ptr(loss2), _lib.ptr(ar["P"]),
-                      _lib.ptr(ar["R"]), _lib.ptr(ar["NBT"]), _lib.ptr(ws), _lib.c_ull(seed),
-                      _lib.c_float(p), _lib.c_float(self._momentum()), _lib.stream_ptr(x.device))
-        self._writeback(ar)
-        torch.autograd.graph.increment_version(ar["R"])
-        if getattr(self, "_keep_ws", False):
-            self._debug = {"plan": plan, "ws": ws, "dt": dt}
-        return loss2, ws, seed, dt, x
+            raise RuntimeError("%s: the fused loss head covers the main output only; with "
+                               "aux=True use forward_loss_aux(x, target, criterion), or "
+                               "%s(aux=True)(model(x), target)" % (who, criterion))
+
+    def _run_forward_loss(self, x, target, spec, ar):
+        """The forward of the fused CE head (``spec``: ``("ce", ignore_index)``).  The head writes
+        ``loss2`` = (mean, count); the backward reads only the count."""
+        self._main_output_only("forward_loss", "MixSoftmaxCrossEntropyLoss")
+        c = self._prologue("forward_loss", x, MODE_TRAIN, ar, target, checks="tensors shape",
+                           check=spec)
+        loss2 = torch.empty(2, dtype=torch.float32, device=c.dev)
+        with torch.cuda.device(c.dev):
+            _lib.call("fscnn_forward_loss", *c.src, _lib.ptr(c.target), int(spec[1]),
+                      _lib.ptr(loss2), *c.mem, *c.end)
+        self._epilogue(c)
+        return loss2, c, _Head("fscnn_backward_loss", (_lib.ptr(loss2),), None, (loss2,))
 
     def _run_forward_loss_dice(self, x, target, spec, ar):
-        """The forward of the fused Dice / Focal+Dice head (``spec``: a Dice ``_head_spec``)."""
-        if self.aux:
-            raise RuntimeError("forward_loss: the fused loss head covers the main output only; "
-                               "with aux=True use forward_loss_aux(x, target, criterion), or "
-                               "MixDiceLoss(aux=True)(model(x), target)")
-        if not x.is_cuda or not target.is_cuda:
-            raise RuntimeError("FastSCNN.forward_loss: the HIP path needs ROCm device tensors")
+        """The forward of the fused Dice / Focal+Dice head (``spec``: a Dice ``_head_spec``); its
+        coefficient planes (``head_ws``) and sums (``stats``) travel to the backward."""
+        self._main_output_only("forward_loss", "MixDiceLoss")
+        refuse = None
         if not 2 <= self.num_classes <= 32:
-            raise RuntimeError("forward_loss: the fused Dice head takes 2 .. 32 classes; use "
-                               "criterion(model(x), target)")
-        nat = self.native()
-        N, _, H, W = x.shape
-        if tuple(target.shape) != (N, H, W):
-            raise RuntimeError("forward_loss: target %s does not match input %s"
-                               % (tuple(target.shape), tuple(x.shape)))
-        if N < 2:
-            raise ValueError("Expected more than 1 value per channel when training, got input "
-                             "size torch.Size([1, 32, 1, 1])")
-        dt = self._compute_dtype(x, True)
-        x = self._input(x)
-        target = target.to(torch.int64).contiguous()
-        from . import loss as _loss
-        if _loss.CHECK_TARGETS:
-            bad = (target < 0) | (target >= self.num_classes)  # no ignore_index in Dice
-            if bool(bad.any()):
-                raise IndexError("Target %d is out of bounds." % int(target[bad].flatten()[0]))
-        plan, fw, _ = nat.plan(N, H, W, _lib.dtype_code(dt), True, x.device)
-        ws = torch.empty(max(fw, 1), dtype=torch.uint8, device=x.device)
-        hb = int(_lib.load().fscnn_dice_head_ws_bytes(plan))
+            refuse = ("forward_loss: the fused Dice head takes 2 .. 32 classes; use "
+                      "criterion(model(x), target)")
+        c = self._prologue("forward_loss", x, MODE_TRAIN, ar, target, refuse=refuse,
+                           checks="tensors shape", check=("dice",))
+        hb = int(_lib.load().fscnn_dice_head_ws_bytes(c.plan))
         if hb < 0:
             _lib.check(hb, "fscnn_dice_head_ws_bytes")
-        head_ws = torch.empty(max(hb, 1), dtype=torch.uint8, device=x.device)
-        stats = torch.empty(4, dtype=torch.float64, device=x.device)
-        loss1 = torch.empty(1, dtype=torch.float32, device=x.device)
-        _, smooth, dw, fw_, alpha, gamma = spec
-        p = self._dropout_p()
-        seed = 0
-        if p > 0:
-            fixed = getattr(self, "_dropout_seed", None)
-            seed = int(fixed) if fixed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
-        with torch.cuda.device(x.device):
-            _lib.call("fscnn_forward_loss_dice", plan, _lib.ptr(x), _lib.dtype_code(x.dtype),
-                      _lib.ptr(target), _lib.c_float(smooth), _lib.c_float(dw), _lib.c_float(fw_),
-                      _lib.c_float(alpha), _lib.c_float(gamma), _lib.ptr(loss1), _lib.ptr(stats),
-                      _lib.ptr(ar["P"]), _lib.ptr(ar["R"]), _lib.ptr(ar["NBT"]), _lib.ptr(ws),
-                      _lib.ptr(head_ws), _lib.c_ull(seed), _lib.c_float(p),
-                      _lib.c_float(self._momentum()), _lib.stream_ptr(x.device))
-        self._writeback(ar)
-        torch.autograd.graph.increment_version(ar["R"])
-        if getattr(self, "_keep_ws", False):
-            self._debug = {"plan": plan, "ws": ws, "dt": dt}
-        return loss1, ws, seed, dt, x, head_ws, stats
+        head_ws = torch.empty(max(hb, 1), dtype=torch.uint8, device=c.dev)
+        stats = torch.empty(4, dtype=torch.float64, device=c.dev)
+        loss1 = torch.empty(1, dtype=torch.float32, device=c.dev)
+        coef = tuple(_lib.c_float(v) for v in spec[1:])  # smooth, dice_weight, focal_weight, ...
+        with torch.cuda.device(c.dev):
+            _lib.call("fscnn_forward_loss_dice", *c.src, _lib.ptr(c.target), *coef,
+                      _lib.ptr(loss1), _lib.ptr(stats), *c.mem, _lib.ptr(head_ws), *c.end)
+        self._epilogue(c)
+        return loss1, c, _Head("fscnn_backward_loss_dice", (_lib.ptr(stats),) + coef[:3], head_ws,
+                               (stats,))
 
     def forward_loss(self, x, target, ignore_index=-1, criterion=None):
         """Fused train-step head: ``criterion(self(x)[0], target)`` of train.py:270-271, computed
@@ -975,12 +908,10 @@ class FastSCNN(nn.Module):
             raise RuntimeError("forward_loss is the training step; call model.train() first")
         if not x.is_cuda:
             raise RuntimeError("FastSCNN.forward_loss: the HIP path needs ROCm device tensors")
-        head = ignore_index
-        if criterion is not None:
-            spec = _head_spec(criterion, ignore_index)
-            head = spec[1] if spec[0] == "ce" else spec
+        spec = _head_spec(criterion, ignore_index)
         ar = self._exec_arena(x.device)
-        return _FastSCNNLossFunction.apply(x, target, head, self, ar, *ar["params"])
+        return _FastSCNNLossFunction.apply(x, target, "forward_loss", spec, self, ar,
+                                           *ar["params"])
 
     def _ohem_weight(self, weight, device):
         """The criterion's class weights as a device fp32 vector, moved once per (tensor,
@@ -1004,61 +935,29 @@ class FastSCNN(nn.Module):
 
     def _run_forward_loss_ohem(self, x, target, spec, ar):
         """The forward of the fused OHEM head (``spec``: an ``_ohem_spec`` tuple whose weights
-        are on the device)."""
-        if self.aux:
-            raise RuntimeError("forward_loss_ohem: the fused loss head covers the main output "
-                               "only; with aux=True use forward_loss_aux(x, target, criterion), "
-                               "or MixSoftmaxCrossEntropyOHEMLoss(aux=True)(model(x), target)")
-        if not x.is_cuda or not target.is_cuda:
-            raise RuntimeError("FastSCNN.forward_loss_ohem: the HIP path needs ROCm device tensors")
-        nat = self.native()
-        N, _, H, W = x.shape
-        if tuple(target.shape) != (N, H, W):
-            raise RuntimeError("forward_loss_ohem: target %s does not match input %s"
-                               % (tuple(target.shape), tuple(x.shape)))
-        if N < 2:
-            raise ValueError("Expected more than 1 value per channel when training, got input "
-                             "size torch.Size([1, 32, 1, 1])")
+        are on the device).  It leaves ``loss2`` and the low-res gradient planes in the CE head's
+        format: same backward."""
         _, ignore_index, thresh, min_kept, weight = spec
-        dt = self._compute_dtype(x, True)
-        x = self._input(x)
-        target = target.to(torch.int64).contiguous()
-        from . import loss as _loss
-        if _loss.CHECK_TARGETS:
-            _loss.check_targets(target, self.num_classes, ignore_index)
-        plan, fw, _ = nat.plan(N, H, W, _lib.dtype_code(dt), True, x.device)
-        dev = x.device
-        ws = torch.empty(max(fw, 1), dtype=torch.uint8, device=dev)
-        loss2 = torch.empty(2, dtype=torch.float32, device=dev)
-        prob = torch.empty(N * H * W, dtype=torch.float32, device=dev)
-        thr = torch.empty(1, dtype=torch.float32, device=dev)
-        counts = torch.empty(2, dtype=torch.int64, device=dev)  # zeroed inside the native run
-        work = torch.empty(2056, dtype=torch.int32, device=dev)
-        p = self._dropout_p()
-        seed = 0
-        if p > 0:
-            fixed = getattr(self, "_dropout_seed", None)
-            seed = int(fixed) if fixed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
-        with torch.cuda.device(dev):
-            rc = _lib.load().fscnn_forward_loss_ohem(
-                plan, _lib.ptr(x), _lib.dtype_code(x.dtype), _lib.ptr(target), int(ignore_index),
-                _lib.c_float(thresh), int(min_kept),
-                _lib.ptr(weight) if weight is not None else None, _lib.ptr(loss2),
-                _lib.ptr(prob), _lib.ptr(thr), _lib.ptr(counts), _lib.ptr(work),
-                _lib.ptr(ar["P"]), _lib.ptr(ar["R"]), _lib.ptr(ar["NBT"]), _lib.ptr(ws),
-                _lib.c_ull(seed), _lib.c_float(p), _lib.c_float(self._momentum()),
-                _lib.stream_ptr(dev))
-        if rc == -2:  # E_UNSUPPORTED: nothing was launched
+        c = self._prologue("forward_loss_ohem", x, MODE_TRAIN, ar, target,
+                           checks="tensors shape", check=("ce", ignore_index))
+        loss2 = torch.empty(2, dtype=torch.float32, device=c.dev)
+        prob = torch.empty(c.N * c.H * c.W, dtype=torch.float32, device=c.dev)
+        thr = torch.empty(1, dtype=torch.float32, device=c.dev)
+        counts = torch.empty(2, dtype=torch.int64, device=c.dev)  # zeroed inside the native run
+        work = torch.empty(2056, dtype=torch.int32, device=c.dev)
+        lib = _lib.load()
+        with torch.cuda.device(c.dev):
+            rc = lib.fscnn_forward_loss_ohem(
+                *c.src, _lib.ptr(c.target), int(ignore_index), _lib.c_float(thresh),
+                int(min_kept), _lib.ptr(weight), _lib.ptr(loss2), _lib.ptr(prob), _lib.ptr(thr),
+                _lib.ptr(counts), _lib.ptr(work), *c.mem, *c.end)
+        if rc == E_UNSUPPORTED:  # nothing was launched
             raise RuntimeError("forward_loss_ohem: no fused OHEM head for this model (%s); use "
                                "the unfused path, criterion(model(x), target)"
-                               % _lib.load().fscnn_last_error().decode(errors="replace"))
+                               % lib.fscnn_last_error().decode(errors="replace"))
         _lib.check(rc, "fscnn_forward_loss_ohem")
-        self._writeback(ar)
-        torch.autograd.graph.increment_version(ar["R"])
-        if getattr(self, "_keep_ws", False):
-            self._debug = {"plan": plan, "ws": ws, "dt": dt,
-                           "ohem": {"prob": prob.view(N, H, W), "thr": thr, "counts": counts}}
-        return loss2, ws, seed, dt, x
+        self._epilogue(c, ohem={"prob": prob.view(c.N, c.H, c.W), "thr": thr, "counts": counts})
+        return loss2, c, _Head("fscnn_backward_loss", (_lib.ptr(loss2),), None, (loss2,))
 
     def forward_loss_ohem(self, x, target, criterion):
         """Fused train-step head for the OHEM criterion: ``criterion(self(x), target)`` of
@@ -1078,39 +977,17 @@ class FastSCNN(nn.Module):
             raise RuntimeError("forward_loss_ohem is the training step; call model.train() first")
         if not x.is_cuda:
             raise RuntimeError("FastSCNN.forward_loss_ohem: the HIP path needs ROCm device tensors")
-        if self.aux:
-            raise RuntimeError("forward_loss_ohem: the fused loss head covers the main output "
-                               "only; with aux=True use forward_loss_aux(x, target, criterion), "
-                               "or MixSoftmaxCrossEntropyOHEMLoss(aux=True)(model(x), target)")
-        head = spec[:4] + (self._ohem_weight(spec[4], x.device),)
+        self._main_output_only("forward_loss_ohem", "MixSoftmaxCrossEntropyOHEMLoss")
+        spec = spec[:4] + (self._ohem_weight(spec[4], x.device),)
         ar = self._exec_arena(x.device)
-        return _FastSCNNLossFunction.apply(x, target, head, self, ar, *ar["params"])
+        return _FastSCNNLossFunction.apply(x, target, "forward_loss_ohem", spec, self, ar,
+                                           *ar["params"])
 
     def _run_forward_loss_aux(self, x, target, spec, ar):
         """The forward of the fused aux loss heads (``spec``: an ``_aux_head_spec`` tuple whose
-        OHEM weights are on the device).  Returns the device ``loss3`` = (total, main, aux), the
-        ``fscnn_aux_head`` struct and the ``head_ws`` buffer the backward takes again."""
+        OHEM weights are on the device).  Its loss is the device ``loss3`` = (total, main, aux);
+        the backward takes the ``fscnn_aux_head`` struct and the ``head_ws`` buffer again."""
         kind, aux_weight = spec[0], spec[1]
-        if not self.aux:
-            raise RuntimeError("forward_loss_aux: this model has no aux head (aux=False); use "
-                               "forward_loss / forward_loss_ohem, or the unfused path, "
-                               "criterion(model(x), target)")
-        if not x.is_cuda or not target.is_cuda:
-            raise RuntimeError("FastSCNN.forward_loss_aux: the HIP path needs ROCm device tensors")
-        if not (2 if kind == "dice" else 1) <= self.num_classes <= 32:
-            raise RuntimeError("forward_loss_aux: the fused heads take 1 .. 32 classes (Dice: "
-                               "2 .. 32); use the unfused path, criterion(model(x), target)")
-        nat = self.native()
-        N, _, H, W = x.shape
-        if tuple(target.shape) != (N, H, W):
-            raise RuntimeError("forward_loss_aux: target %s does not match input %s"
-                               % (tuple(target.shape), tuple(x.shape)))
-        if N < 2:
-            raise ValueError("Expected more than 1 value per channel when training, got input "
-                             "size torch.Size([1, 32, 1, 1])")
-        dt = self._compute_dtype(x, True)
-        x = self._input(x)
-        target = target.to(torch.int64).contiguous()
         head = _lib.AuxHead()
         head.aux_weight = aux_weight
         head.ignore_index = -1
@@ -1123,57 +1000,47 @@ class FastSCNN(nn.Module):
             _, _, ign, thresh, min_kept, weight = spec
             head.head, head.ignore_index, head.thresh, head.min_kept = 2, ign, thresh, min_kept
             head.class_weight = weight.data_ptr() if weight is not None else None
-        from . import loss as _loss
-        if _loss.CHECK_TARGETS:
-            if kind == "dice":  # no ignore_index in Dice
-                bad = (target < 0) | (target >= self.num_classes)
-                if bool(bad.any()):
-                    raise IndexError("Target %d is out of bounds." % int(target[bad].flatten()[0]))
-            else:
-                _loss.check_targets(target, self.num_classes, int(head.ignore_index))
-        dev = x.device
-        plan, fw, _ = nat.plan(N, H, W, _lib.dtype_code(dt), True, dev)
-        hb = int(_lib.load().fscnn_aux_head_ws_bytes(plan, head.head))
+        refuse = None
+        if not (2 if kind == "dice" else 1) <= self.num_classes <= 32:
+            refuse = ("forward_loss_aux: the fused heads take 1 .. 32 classes (Dice: 2 .. 32); "
+                      "use the unfused path, criterion(model(x), target)")
+        c = self._prologue("forward_loss_aux", x, MODE_TRAIN, ar, target, refuse=refuse,
+                           checks="tensors shape",
+                           check=("dice",) if kind == "dice" else ("ce", int(head.ignore_index)))
+        lib = _lib.load()
+        hb = int(lib.fscnn_aux_head_ws_bytes(c.plan, head.head))
         if hb < 0:
             _lib.check(hb, "fscnn_aux_head_ws_bytes")
-        ws = torch.empty(max(fw, 1), dtype=torch.uint8, device=dev)
-        head_ws = torch.empty(hb, dtype=torch.uint8, device=dev)
-        loss3 = torch.empty(3, dtype=torch.float32, device=dev)
-        p = self._dropout_p()
-        seed = 0
-        if p > 0:
-            fixed = getattr(self, "_dropout_seed", None)
-            seed = int(fixed) if fixed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
-        with torch.cuda.device(dev):
-            rc = _lib.load().fscnn_forward_loss_aux(
-                plan, _lib.ptr(x), _lib.dtype_code(x.dtype), _lib.ptr(target),
-                _lib.ctypes.byref(head), _lib.ptr(loss3), _lib.ptr(ar["P"]), _lib.ptr(ar["R"]),
-                _lib.ptr(ar["NBT"]), _lib.ptr(ws), _lib.ptr(head_ws), _lib.c_ull(seed),
-                _lib.c_float(p), _lib.c_float(self._momentum()), _lib.stream_ptr(dev))
+        head_ws = torch.empty(hb, dtype=torch.uint8, device=c.dev)
+        loss3 = torch.empty(3, dtype=torch.float32, device=c.dev)
+        with torch.cuda.device(c.dev):
+            rc = lib.fscnn_forward_loss_aux(*c.src, _lib.ptr(c.target), _lib.ctypes.byref(head),
+                                            _lib.ptr(loss3), *c.mem, _lib.ptr(head_ws), *c.end)
         if rc == E_UNSUPPORTED:  # nothing was launched
             raise RuntimeError("forward_loss_aux: no fused aux loss heads for this model (%s); "
                                "use the unfused path, criterion(model(x), target)"
-                               % _lib.load().fscnn_last_error().decode(errors="replace"))
+                               % lib.fscnn_last_error().decode(errors="replace"))
         _lib.check(rc, "fscnn_forward_loss_aux")
-        self._writeback(ar)
-        torch.autograd.graph.increment_version(ar["R"])
-        if getattr(self, "_keep_ws", False):
-            self._debug = {"plan": plan, "ws": ws, "dt": dt, "head_ws": head_ws}
-            if kind == "ohem":  # each head's plane, threshold and counters, as views of head_ws
-                def view(field, which, n, tdt):
-                    off = int(_lib.load().fscnn_aux_head_ws_offset(plan, 2, field, which))
-                    if off < 0:
-                        _lib.check(off, "fscnn_aux_head_ws_offset")
-                    nb = n * torch.tensor([], dtype=tdt).element_size()
-                    return head_ws[off:off + nb].view(tdt)
-                self._debug["ohem"] = [{"prob": view(b"prob", i, N * H * W, torch.float32)
-                                        .view(N, H, W),
-                                        "thr": view(b"thr", i, 1, torch.float32),
-                                        "counts": view(b"counts", i, 2, torch.int64),
-                                        # (weighted mean, sum of the kept pixels' weights)
-                                        "pair": view(b"pair", i, 2, torch.float32)}
-                                       for i in range(2)]
-        return loss3, ws, seed, dt, x, head, head_ws
+        debug = {"head_ws": head_ws}
+        if kind == "ohem" and getattr(self, "_keep_ws", False):
+            # each head's plane, threshold and counters, as views of head_ws
+            def view(field, which, n, tdt):
+                off = int(lib.fscnn_aux_head_ws_offset(c.plan, 2, field, which))
+                if off < 0:
+                    _lib.check(off, "fscnn_aux_head_ws_offset")
+                nb = n * torch.tensor([], dtype=tdt).element_size()
+                return head_ws[off:off + nb].view(tdt)
+            debug["ohem"] = [{"prob": view(b"prob", i, c.N * c.H * c.W, torch.float32)
+                              .view(c.N, c.H, c.W),
+                              "thr": view(b"thr", i, 1, torch.float32),
+                              "counts": view(b"counts", i, 2, torch.int64),
+                              # (weighted mean, sum of the kept pixels' weights)
+                              "pair": view(b"pair", i, 2, torch.float32)}
+                             for i in range(2)]
+        self._epilogue(c, **debug)
+        # (spec: the OHEM class weights the struct points to stay alive until the backward)
+        return loss3, c, _Head("fscnn_backward_loss_aux", (_lib.ctypes.byref(head),), head_ws,
+                               (head, spec))
 
     def forward_loss_aux(self, x, target, criterion):
         """Fused train-step heads of an ``aux=True`` model: ``criterion(self(x), target)`` =
@@ -1203,19 +1070,21 @@ class FastSCNN(nn.Module):
         if spec[0] == "ohem":
             spec = spec[:5] + (self._ohem_weight(spec[5], x.device),)
         ar = self._exec_arena(x.device)
-        return _FastSCNNAuxLossFunction.apply(x, target, spec, self, ar, *ar["params"])
+        return _FastSCNNLossFunction.apply(x, target, "forward_loss_aux", spec, self, ar,
+                                           *ar["params"])
 
-    def _run_backward(self, gout, x, ws, seed, dt, ar, gloss=None, loss2=None, gaux=None,
-                      mode=MODE_TRAIN, dx=None, dice=None, aux_head=None):
+    def _run_backward(self, gout, x, ws, seed, dt, ar, gloss=None, gaux=None, mode=MODE_TRAIN,
+                      dx=None, head=None):
         """The staged native backward of a MODE_TRAIN / MODE_EVAL_GRAD forward whose workspace
         is ``ws``; parameter gradients are views of one flat arena G, and ``dx`` (dense NCHW,
-        the dtype of ``x``) receives the input gradient when given."""
+        the dtype of ``x``) receives the input gradient when given.  ``head``: the ``_Head`` of a
+        fused loss forward (then ``gloss`` is d(loss)), or None for the gradients of the logits."""
         nat = self.native()
         N, _, H, W = x.shape
         plan, _, bw = nat.plan(N, H, W, _lib.dtype_code(dt), mode, x.device)
         if gout is not None:
             gout = gout.to(dt).contiguous()
-        if self.aux and gloss is None:
+        if self.aux and head is None:
             gaux = torch.zeros_like(gout) if gaux is None else gaux.to(dt).contiguous()
         # every element of every parameter's gradient is written by the backward (a reduction,
         # a BN finish or the PPM kernel; tests/test_gpu_model.py fills G with NaN to check), so
@@ -1228,61 +1097,43 @@ class FastSCNN(nn.Module):
         if getattr(self, "_keep_ws", False):
             self._debug["bws"] = bws
         hook = self.grad_stage_hook
-        if hook is None:
-            # one native call for the four stages: their weight-gradient reductions run once at
-            # its end, so the main stream does not wait for the side stream between stages
+        # without a hook, one native call for the four stages: their weight-gradient reductions
+        # run once at its end, so the main stream does not wait for the side stream between stages
+        for s0, s1 in [(0, 3)] if hook is None else [(s, s) for s in range(4)]:
             with torch.cuda.device(x.device):
-                self._backward_stage(plan, (0, 3), gout, gaux, gloss, loss2, x, ar, G, ws, bws,
-                                     seed, p, dx, dice, aux_head)
-        else:
-            for s in range(4):
-                with torch.cuda.device(x.device):
-                    self._backward_stage(plan, (s, s), gout, gaux, gloss, loss2, x, ar, G, ws,
-                                         bws, seed, p, dx, dice, aux_head)
-                b, e = nat.stage_ranges[s]
-                hook(s, G, b, e)
+                self._backward_stage(plan, (s0, s1), gout, gaux, gloss, head, x, ar, G, ws, bws,
+                                     seed, p, dx)
+            if hook is not None:
+                b, e = nat.stage_ranges[s0]
+                hook(s0, G, b, e)
         return [G[off:off + numel].view(prm.shape)
                 for prm, (_, off, numel) in zip(ar["params"], nat.params)]
 
-    def _backward_stage(self, plan, stages, gout, gaux, gloss, loss2, x, ar, G, ws, bws, seed, p,
-                        dx=None, dice=None, aux_head=None):
-        s0, s1 = stages  # backward stages s0 .. s1 (0: head ... 3: LearningToDownsample)
-        if aux_head is not None:  # the fused aux loss heads: (struct, head_ws, spec) of the forward
-            head, head_ws, _ = aux_head
-            _lib.call("fscnn_backward_loss_aux", plan, _lib.ptr(gloss), _lib.ctypes.byref(head),
-                      _lib.ptr(x), _lib.dtype_code(x.dtype), _lib.ptr(dx),
-                      _lib.dtype_code(dx.dtype if dx is not None else x.dtype),
-                      _lib.ptr(ar["P"]), _lib.ptr(G), _lib.ptr(ws), _lib.ptr(bws),
-                      _lib.ptr(head_ws), _lib.c_ull(seed), _lib.c_float(p), s0, s1,
-                      _lib.stream_ptr(x.device))
-        elif dice is not None:  # the fused Dice head: (spec, head_ws, stats) of its forward
-            (_, smooth, dw, fw, _, _), head_ws, stats = dice
-            _lib.call("fscnn_backward_loss_dice", plan, _lib.ptr(gloss), _lib.ptr(stats),
-                      _lib.c_float(smooth), _lib.c_float(dw), _lib.c_float(fw), _lib.ptr(x),
-                      _lib.dtype_code(x.dtype), _lib.ptr(ar["P"]), _lib.ptr(G), _lib.ptr(ws),
-                      _lib.ptr(bws), _lib.ptr(head_ws), _lib.c_ull(seed), _lib.c_float(p), s0, s1,
-                      _lib.stream_ptr(x.device))
-        elif dx is not None:  # the general entry point: also writes the input gradient (stage 3)
-            _lib.call("fscnn_backward_dx", plan, _lib.ptr(gout), _lib.ptr(gaux), _lib.ptr(gloss),
-                      _lib.ptr(loss2), _lib.ptr(x), _lib.dtype_code(x.dtype), _lib.ptr(dx),
-                      _lib.dtype_code(dx.dtype), _lib.ptr(ar["P"]), _lib.ptr(G), _lib.ptr(ws),
-                      _lib.ptr(bws), _lib.c_ull(seed), _lib.c_float(p), s0, s1,
-                      _lib.stream_ptr(x.device))
-        elif gloss is None and self.aux:
-            _lib.call("fscnn_backward_aux", plan, _lib.ptr(gout), _lib.ptr(gaux), _lib.ptr(x),
-                      _lib.dtype_code(x.dtype), _lib.ptr(ar["P"]), _lib.ptr(G), _lib.ptr(ws),
-                      _lib.ptr(bws), _lib.c_ull(seed), _lib.c_float(p), s0, s1,
-                      _lib.stream_ptr(x.device))
-        elif gloss is None:
-            _lib.call("fscnn_backward", plan, _lib.ptr(gout), _lib.ptr(x),
-                      _lib.dtype_code(x.dtype), _lib.ptr(ar["P"]), _lib.ptr(G), _lib.ptr(ws),
-                      _lib.ptr(bws), _lib.c_ull(seed), _lib.c_float(p), s0, s1,
-                      _lib.stream_ptr(x.device))
+    def _backward_stage(self, plan, stages, gout, gaux, gloss, head, x, ar, G, ws, bws, seed, p,
+                        dx=None):
+        """Backward stages s0 .. s1 (0: head ... 3: LearningToDownsample) by the C entry the
+        forward's head names; every entry ends in the same arguments."""
+        xa = (_lib.ptr(x), _lib.dtype_code(x.dtype))
+        dxa = (_lib.ptr(dx), _lib.dtype_code(dx.dtype if dx is not None else x.dtype))
+        mem = (_lib.ptr(ar["P"]), _lib.ptr(G), _lib.ptr(ws), _lib.ptr(bws))
+        end = (_lib.c_ull(seed), _lib.c_float(p)) + tuple(stages) + (_lib.stream_ptr(x.device),)
+        if head is None:  # from the gradients of the logits
+            if dx is not None:  # the general entry point: also writes the input gradient (stage 3)
+                _lib.call("fscnn_backward_dx", plan, _lib.ptr(gout), _lib.ptr(gaux), None, None,
+                          *xa, *dxa, *mem, *end)
+            elif self.aux:
+                _lib.call("fscnn_backward_aux", plan, _lib.ptr(gout), _lib.ptr(gaux), *xa, *mem,
+                          *end)
+            else:
+                _lib.call("fscnn_backward", plan, _lib.ptr(gout), *xa, *mem, *end)
+        elif head.entry == "fscnn_backward_loss" and dx is not None:  # (the general entry again)
+            _lib.call("fscnn_backward_dx", plan, None, None, _lib.ptr(gloss), *head.lead, *xa,
+                      *dxa, *mem, *end)
         else:
-            _lib.call("fscnn_backward_loss", plan, _lib.ptr(gloss), _lib.ptr(loss2), _lib.ptr(x),
-                      _lib.dtype_code(x.dtype), _lib.ptr(ar["P"]), _lib.ptr(G), _lib.ptr(ws),
-                      _lib.ptr(bws), _lib.c_ull(seed), _lib.c_float(p), s0, s1,
-                      _lib.stream_ptr(x.device))
+            takes_dx = head.entry == "fscnn_backward_loss_aux"
+            hws = () if head.head_ws is None else (_lib.ptr(head.head_ws),)
+            _lib.call(head.entry, plan, _lib.ptr(gloss), *head.lead, *xa,
+                      *(dxa if takes_dx else ()), *mem, *hws, *end)
 
     def _needs_graph(self, x):
         """Whether this call is differentiable, as the reference's would be: train mode with
