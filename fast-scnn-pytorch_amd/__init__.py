@@ -12,8 +12,9 @@ Submodules:
   optim          fused multi-tensor SGD and AdamW (HIP)
   ddp            one-process-per-GPU data parallel with bucketed RCCL gradient all-reduce
   deploy         EndToEndFastSCNN — the deployment model: raw frames in, probabilities / mask out
-  bev            BirdEyeView / centerline — calibration, view parameters and the centreline read
-                 from the row table of EndToEndFastSCNN.bird_eye
+  bev            BirdEyeView / centerline / warp_image — calibration, view parameters, the
+                 centreline read from the row table of EndToEndFastSCNN.bird_eye, and the colour
+                 bird's-eye view of a camera frame (EndToEndFastSCNN.bird_eye_view)
   path           plan / PathPlanner / VisualLateralErrorController — the steering tail: row table
                  -> fitted path -> wheel PWM in one launch (EndToEndFastSCNN.steer runs it behind
                  the bird's-eye tail)
@@ -21,7 +22,7 @@ Submodules:
                  (EndToEndFastSCNN.overlay is the same blend fused behind the backbone)
 """
 __all__ = ["FastSCNN", "get_fast_scnn", "EndToEndFastSCNN", "BirdEyeView", "centerline",
-           "overlay_mask"]
+           "overlay_mask", "warp_image"]
 
 
 def __getattr__(name):
@@ -31,7 +32,7 @@ def __getattr__(name):
     if name == "EndToEndFastSCNN":
         from . import deploy
         return deploy.EndToEndFastSCNN
-    if name in ("BirdEyeView", "centerline"):
+    if name in ("BirdEyeView", "centerline", "warp_image"):
         from . import bev
         return getattr(bev, name)
     if name == "overlay_mask":

@@ -106,6 +106,8 @@ SIGNATURES = {
     "fscnn_forward_e2e_bev": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, P_float,
                                       P_float, c_int, c_int, c_int, P_double, c_int, c_int, c_int,
                                       c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "fscnn_bev_image": (c_int, [c_vp, c_int, c_int, c_int, c_int, P_double, c_int, c_int, c_vp,
+                                c_vp, P_ubyte, c_float, c_float, c_float, c_vp, c_vp]),
     "fscnn_path_plan": (c_int, [c_vp, c_int, c_int, P_path_params, c_vp, c_vp, c_vp]),
     "fscnn_overlay_mask": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_int,
                                    P_ubyte, c_vp, c_int, c_float, c_float, c_float, c_vp, c_vp,

@@ -12,15 +12,18 @@ Restates, without OpenCV, what the reference's consumers do around the lane mask
   (``kuruma/vision/path_planning.py:188-314``) -> ``centerline``, read from the row table that
   ``EndToEndFastSCNN.bird_eye`` (``csrc/bev.hip``) leaves, instead of a Python loop over pixels.
 
-The warp itself and the row scan run on the device; this module is host arithmetic on 3 x 3
-matrices and on ``Hb x 4`` integers.  Path smoothing, waypoints and the wheel PWM follow in
+The warps and the row scan run on the device -- the mask by the nearest neighbour
+(``warp_mask``, ``csrc/bev.hip``), the camera frame bilinearly with the segmented picture in the
+same launch (``warp_image``, ``csrc/bev_image.hip``) -- and this module is otherwise host arithmetic
+on 3 x 3 matrices and on ``Hb x 4`` integers.  Path smoothing, waypoints and the wheel PWM follow in
 ``path`` (``csrc/path.hip``), which reads the same row table on the device;
 ``EndToEndFastSCNN.steer`` runs both behind the backbone.
 """
 import numpy as np
 
-__all__ = ["BirdEyeView", "centerline", "warp_mask", "get_builtin_calibration", "get_corrected_calibration",
-           "perspective_transform", "inverse_map", "MAX_WIDTH", "MAX_HEIGHT"]
+__all__ = ["BirdEyeView", "centerline", "warp_mask", "warp_image", "get_builtin_calibration",
+           "get_corrected_calibration", "perspective_transform", "inverse_map", "MAX_WIDTH",
+           "MAX_HEIGHT"]
 
 MAX_WIDTH, MAX_HEIGHT = 8192, 65535  # of a bird's-eye view the kernel takes (include/fastscnn.h)
 
@@ -90,8 +93,9 @@ def get_corrected_calibration():
 
 
 class BirdEyeView:
-    """``PerspectiveTransformer(calibration_data=None, use_corrected=True)`` of the reference,
-    without the image warp: it produces the view parameters ``EndToEndFastSCNN.bird_eye`` takes."""
+    """``PerspectiveTransformer(calibration_data=None, use_corrected=True)`` of the reference: it
+    produces the view parameters ``EndToEndFastSCNN.bird_eye`` takes, and
+    ``transform_image_and_mask`` warps a frame and its mask on the device."""
 
     def __init__(self, calibration=None, use_corrected=True):
         if calibration is None:
@@ -155,6 +159,45 @@ class BirdEyeView:
         }
         return (out_w, out_h), combined, bounds, view_params
 
+    def transform_image_and_mask(self, image, mask, pixels_per_unit=20, margin_ratio=0.1,
+                                 full_image=True):
+        """transform.py:130-201 on the device: ``(bird_eye_image, bird_eye_mask, view_params)``.
+
+        ``image`` is a uint8 camera frame ``[H, W, 3]`` and ``mask`` its uint8 lane mask ``[H, W]``
+        on a ROCm device, or batches ``[N, H, W, 3]`` / ``[N, H, W]``; the results have the same
+        batching.  The image is warped bilinearly (``warp_image``), the mask by the nearest
+        neighbour (``warp_mask``), both with border 0 and with the matrix rescaled when the source
+        is not the calibration size, as ``params(source_size=...)`` does.  Two launches:
+        ``fscnn_bev_image`` and ``fscnn_bev_mask``."""
+        import torch
+        who = "transform_image_and_mask"
+        if not isinstance(image, torch.Tensor) or not isinstance(mask, torch.Tensor):
+            raise RuntimeError("%s: image and mask are torch tensors on a ROCm device" % who)
+        if image.dtype != torch.uint8 or mask.dtype != torch.uint8:
+            raise RuntimeError("%s: image and mask are uint8, not %s / %s: a float image would "
+                               "take OpenCV's float bilinear law, which this is not"
+                               % (who, image.dtype, mask.dtype))
+        batched = image.dim() == 4
+        if image.dim() not in (3, 4) or image.shape[-1] != 3 or mask.dim() != image.dim() - 1:
+            raise RuntimeError("%s: expected an image [H, W, 3] with a mask [H, W], or batches "
+                               "[N, H, W, 3] / [N, H, W]; got %s and %s"
+                               % (who, tuple(image.shape), tuple(mask.shape)))
+        if not batched:
+            image, mask = image[None], mask[None]
+        if tuple(mask.shape) != tuple(image.shape[:3]):
+            raise RuntimeError("%s: the mask %s does not match the image %s"
+                               % (who, tuple(mask.shape), tuple(image.shape)))
+        h, w = int(image.shape[1]), int(image.shape[2])
+        size, _, _, view_params = self.params(pixels_per_unit, margin_ratio, full_image,
+                                              source_size=(w, h))
+        _view_size(size, who)
+        m = inverse_map(view_params)
+        bird = warp_image(image, m, size, channels_last=True)
+        bird_mask, _ = warp_mask(mask, m, size)
+        if not batched:
+            bird, bird_mask = bird[0], bird_mask[0]
+        return bird, bird_mask, view_params
+
 
 def inverse_map(view_params):
     """The destination -> source matrix of a view as 9 float64 values: the inverse of
@@ -191,6 +234,81 @@ def warp_mask(mask, m, size, min_width=10, return_mask=True):
                   hb, wb, int(min_width), _lib.ptr(bev), _lib.ptr(rows),
                   _lib.stream_ptr(mask.device))
     return bev, rows
+
+
+def _view_size(size, who):
+    wb, hb = int(size[0]), int(size[1])
+    if not (1 <= wb <= MAX_WIDTH and 1 <= hb <= MAX_HEIGHT):
+        raise RuntimeError("%s: view %d x %d: the bird's-eye kernels take widths 1 .. %d and "
+                           "heights 1 .. %d" % (who, wb, hb, MAX_WIDTH, MAX_HEIGHT))
+    return wb, hb
+
+
+def warp_image(frames, m, size, channels_last=None, mask=None, alpha=0.5, color=(0, 255, 0),
+               frame_weight=1.0, gamma=0.0):
+    """The colour bird's-eye view (``fscnn_bev_image``, ``csrc/bev_image.hip``): uint8 ``frames``
+    ``[N, 3, h, w]`` or ``[N, h, w, 3]`` on a ROCm device warped to ``size`` = (Wb, Hb) with the
+    fixed-point bilinear law of ``include/fastscnn.h`` (``cv2.warpPerspective`` with
+    ``INTER_LINEAR`` and border 0), ``m`` the 9 destination -> source values
+    (``inverse_map(view_params)``).  Returns ``image``, uint8 in the layout of the frames.
+
+    ``channels_last=None`` reads the layout off the shape: ``[N, h, w, 3]`` when only the last
+    dimension is 3, ``[N, 3, h, w]`` otherwise (so pass it when both are 3); ``True`` / ``False``
+    are checked as ``vis.overlay_mask`` checks them.  Channels are never swapped.
+
+    With ``mask`` (uint8 ``[N, Hb, Wb]``, a bird's-eye mask such as ``warp_mask``'s) the same launch
+    also writes the segmented picture, the reference's ``create_visualization(bird_eye_image,
+    bird_eye_mask)``: ``color`` (in the frames' channel order) where the mask is not 0, blended as
+    ``image * frame_weight + colour * alpha + gamma`` by the overlay law; the result is then
+    ``(image, blended)``.  Float frames are refused: OpenCV warps them by a different law."""
+    import ctypes
+
+    import torch
+
+    from . import _lib
+    from . import vis as _vis
+    who = "warp_image"
+    if isinstance(frames, torch.Tensor) and frames.dtype != torch.uint8:
+        raise RuntimeError("%s: frames are uint8, not %s: the law is OpenCV's fixed-point remap of "
+                           "8-bit images, and a float frame would take another law"
+                           % (who, frames.dtype))
+    if not isinstance(frames, torch.Tensor) or frames.dim() != 4:
+        raise RuntimeError("%s: expected 4-d frames" % who)
+    if channels_last is None:
+        channels_last = frames.shape[3] == 3 and frames.shape[1] != 3
+    if frames.shape[3 if channels_last else 1] != 3:
+        raise RuntimeError("%s: expected frames %s, got %s"
+                           % (who, "[N, h, w, 3]" if channels_last else "[N, 3, h, w]",
+                              tuple(frames.shape)))
+    wb, hb = _view_size(size, who)
+    frames, n, h, w = _vis.check_frames(frames, bool(channels_last), who)
+    if n > 65535 or h > 16384 or w > 16384:
+        raise RuntimeError("%s: frames %s: at most 65535 frames with sides up to 16384"
+                           % (who, tuple(frames.shape)))
+    m9 = np.asarray(m, dtype=np.float64).reshape(-1)
+    if m9.size != 9 or not np.isfinite(m9).all():
+        raise RuntimeError("%s: m is 9 finite destination -> source values" % who)
+    dev = frames.device
+    c3 = None
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or \
+                tuple(mask.shape) != (n, hb, wb):
+            raise RuntimeError("%s: the mask is the uint8 bird's-eye mask [%d, %d, %d], got %s"
+                               % (who, n, hb, wb, getattr(mask, "shape", type(mask))))
+        if mask.device != dev:
+            raise RuntimeError("%s: the HIP path needs the mask on the frames' ROCm device (got %s "
+                               "and %s)" % (who, mask.device, dev))
+        mask = mask.contiguous()
+        c3 = (ctypes.c_ubyte * 3)(*_vis._color3(color))
+    shape = (n, hb, wb, 3) if channels_last else (n, 3, hb, wb)
+    image = torch.empty(shape, dtype=torch.uint8, device=dev)
+    blended = torch.empty(shape, dtype=torch.uint8, device=dev) if mask is not None else None
+    cm = (ctypes.c_double * 9)(*[float(v) for v in m9])
+    with torch.cuda.device(dev):
+        _lib.call("fscnn_bev_image", _lib.ptr(frames), int(bool(channels_last)), n, h, w, cm, hb,
+                  wb, _lib.ptr(image), _lib.ptr(mask), c3, float(frame_weight), float(alpha),
+                  float(gamma), _lib.ptr(blended), _lib.stream_ptr(dev))
+    return image if mask is None else (image, blended)
 
 
 def centerline(rows, view_params, fast=False, min_width=None, skip_rows=None,

@@ -12,8 +12,9 @@
 // ee_pixel (e2e_pixel.hpp) -- the frame-size mask is never written.  The gather reads the
 // low-resolution logits from global memory: N x (base/8)^2 x C values, which stay in L2.
 //
-// Coordinate law (include/fastscnn.h), in fp64 with every operation rounded on its own (bv_source),
-// so that a float64 numpy restatement gives the same integers.
+// Coordinate law (include/fastscnn.h), in fp64 with every operation rounded on its own (bv_source
+// of bev_coord.hpp), so that a float64 numpy restatement gives the same integers.
+#include "bev_coord.hpp"
 #include "e2e_pixel.hpp"
 
 #include <climits>
@@ -23,35 +24,6 @@ namespace fscnn {
 
 constexpr int BV_T = 256;
 constexpr int BV_WORDS = BEV_MAXW / 64;
-
-// The law for destination pixel (x, y); m1y, m4y, m7y = the row's m1*y, m4*y, m7*y (bv_mul).
-// hipcc contracts a * b + c into an fma by default, and through __dmul_rn / __dadd_rn too: their
-// bodies are plain operators compiled under the same default (the ISA showed v_fma_f64 for
-// m0*x + m1*y with them).  So the products and sums are written as operators inside blocks with
-// contraction switched off, which is what keeps every operation rounded on its own; the ISA of
-// these kernels holds no v_fma_f64 outside the division's refinement sequence.
-__device__ __forceinline__ double bv_mul(double a, double b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
-__device__ __forceinline__ void bv_source(const double* m, int x, double m1y, double m4y,
-                                          double m7y, int& sx, int& sy) {
-#pragma clang fp contract(off)
-  const double dx = (double)x;
-  const double X = (m[0] * dx + m1y) + m[2];
-  const double Y = (m[3] * dx + m4y) + m[5];
-  double W = (m[6] * dx + m7y) + m[8];
-  W = W != 0.0 ? 1.0 / W : 0.0;  // (IEEE division: no fast-math flag in this build)
-  // clamp to the int range the way std::max(INT_MIN, std::min(INT_MAX, v)) does (a NaN ends as
-  // INT_MAX, which no source has), then round half to even
-  double fx = X * W, fy = Y * W;
-  fx = fx < (double)INT_MAX ? fx : (double)INT_MAX;
-  fy = fy < (double)INT_MAX ? fy : (double)INT_MAX;
-  fx = fx > (double)INT_MIN ? fx : (double)INT_MIN;
-  fy = fy > (double)INT_MIN ? fy : (double)INT_MIN;
-  sx = (int)rint(fx);
-  sy = (int)rint(fy);
-}
 
 struct BvMaskSrc {
   const uint8_t* mask;

@@ -633,6 +633,29 @@ int fscnn_path_plan(const int* rows, int N, int Hb, const fscnn_path_params* p, 
   return path_plan(rows, N, Hb, *p, ema_state, out, S(stream));
 }
 
+// ---- colour bird's-eye view (bev_image.hip) --------------------------------------------------------
+int fscnn_bev_image(const unsigned char* frames, int channels_last, int N, int h, int w,
+                    const double* m, int Hb, int Wb, unsigned char* image,
+                    const unsigned char* bev_mask, const unsigned char* color, float frame_weight,
+                    float alpha, float gamma, unsigned char* blended, void* stream) {
+  if (!frames || !m) {
+    set_error("fscnn_bev_image: null argument");
+    return E_INVALID;
+  }
+  if (blended && (!bev_mask || !color)) {
+    set_error("fscnn_bev_image: the blended output needs bev_mask and color");
+    return E_INVALID;
+  }
+  BevImageArgs a{};
+  a.frames = frames; a.channels_last = channels_last != 0; a.N = N; a.h = h; a.w = w;
+  a.Hb = Hb; a.Wb = Wb; a.image = image; a.blended = blended;
+  a.bev_mask = blended ? bev_mask : nullptr;
+  for (int i = 0; i < 9; ++i) a.m[i] = m[i];
+  for (int k = 0; k < 3; ++k) a.color[k] = blended ? color[k] : 0;
+  a.frame_weight = frame_weight; a.alpha = alpha; a.gamma = gamma;
+  return bev_image(a, S(stream));
+}
+
 // ---- overlay tail (overlay.hip) --------------------------------------------------------------------
 static int overlay_args(const char* who, const void* frames, int frame_dtype, int channels_last,
                         int N, int h, int w, float frame_weight, float alpha, float gamma,

@@ -811,6 +811,21 @@ int overlay_mask(const OverlayArgs& a, const uint8_t* mask, int Hm, int Wm,
                  const OverlayColors& colors, const uint8_t* palette, int P, hipStream_t st);
 int e2e_overlay(const E2eHeadArgs& h, const OverlayArgs& a, const OverlayColors& colors, int dtype,
                 hipStream_t st);
+// Colour bird's-eye view (bev_image.hip): the uint8 camera frames warped to Hb x Wb with the
+// fixed-point bilinear law of include/fastscnn.h, and / or that warped frame blended with `color`
+// where bev_mask is set (the overlay law's lane mode), in one launch.
+struct BevImageArgs {
+  const uint8_t* frames;  // [N][h][w][3] (channels_last) or [N][3][h][w]
+  int channels_last, N, h, w, Hb, Wb;
+  double m[9];              // destination -> source
+  uint8_t* image;           // layout of the frames, or null
+  const uint8_t* bev_mask;  // [N][Hb][Wb]; needed by blended
+  uint8_t color[3];
+  float frame_weight, alpha, gamma;
+  uint8_t* blended;  // layout of the frames, or null (not both)
+};
+bool bev_image_ok(int N, int h, int w, int Hb, int Wb);
+int bev_image(const BevImageArgs& a, hipStream_t st);
 // Steering tail (path.hip): row table -> centreline -> QR polynomial fit -> waypoints -> preview
 // point -> EMA -> wheel PWM, one workgroup per frame (include/fastscnn.h: the law, the record).
 // ema_state: device double [N][2] or null; out: device double [N][FSCNN_PATH_REC + 2 * K].

@@ -3,7 +3,8 @@
 // kuruma/core/preprocessing.py:85-104: green where mask > 0, cv2.addWeighted(frame, 1, green,
 // alpha, 0); the evaluation scripts: a per-class colour image at 0.7 / 0.3 or 0.6 / 0.4), after the
 // nearest-neighbour resize of the mask back to the camera frame (postprocess_matched_resolution,
-// :53-79).  The law is stated in include/fastscnn.h; ov_src / ov_blend are its two halves.
+// :53-79).  The law is stated in include/fastscnn.h; ov_src / ov_blend (overlay_blend.hpp) are its
+// two halves.
 //   overlay_mask   frames + a uint8 mask in memory: pure streaming, a thread owns 4 consecutive
 //                  pixels of a frame row
 //   e2e_overlay    frames + the low-resolution logits: a workgroup owns OV_TW x OV_TH frame pixels,
@@ -15,6 +16,7 @@
 //                  thread with the routine overlay_mask uses.  Neither a mask nor a probability is
 //                  written unless the caller asks for the frame-size mask.
 #include "e2e_pixel.hpp"
+#include "overlay_blend.hpp"
 
 #include <algorithm>
 
@@ -26,21 +28,6 @@ constexpr int OV_TW = 64, OV_TH = 4, OV_T = OV_TW * OV_TH;
 // source index of frame index x: floor(x * M / w) as a rational (cv2.INTER_NEAREST), x * M < 2^28
 __host__ __device__ __forceinline__ int ov_src(int x, int M, int w) {
   return M == w ? x : (int)((unsigned)(x * M) / (unsigned)w);
-}
-
-// t = ((a * fw) + (o * alpha)) + gamma, each operation rounded to fp32 on its own, then
-// saturate_cast<uchar>: round half to even, clamp, NaN -> 0.  Plain operators under contract(off):
-// hipcc's default contraction reaches through __fmul_rn / __fadd_rn (common.hpp lerp2), and a fused
-// a * 1 + 127.5 would round differently from the law.
-__device__ __forceinline__ uint8_t ov_blend(float a, float o, float fw, float alpha, float gamma) {
-#pragma clang fp contract(off)
-  const float p = a * fw;
-  const float q = o * alpha;
-  const float s = p + q;
-  float t = rintf(s + gamma);
-  t = t > 0.f ? t : 0.f;  // (a NaN fails the comparison)
-  t = t < 255.f ? t : 255.f;
-  return (uint8_t)(int)t;
 }
 
 __device__ __forceinline__ float ov_ld(const uint8_t* p) { return (float)*p; }

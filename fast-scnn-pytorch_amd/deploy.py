@@ -21,7 +21,9 @@ full-resolution logits nor, for ``predict``, any probability is ever formed.
 ``bird_eye`` is a second tail (``csrc/bev.hip``) for what the car's code does next with the lane
 mask (``kuruma/vision/transform.py:130-201``, ``path_planning.py:188-293``): from the same
 1/8-resolution logits straight to the bird's-eye mask and the per-row table the centreline is
-read from (``bev.centerline``), without writing the frame-size mask.
+read from (``bev.centerline``), without writing the frame-size mask.  ``bird_eye_view`` adds the
+other half of ``transform_image_and_mask``, the camera frame warped bilinearly to the same view,
+and the segmented bird's-eye picture, in one more launch (``csrc/bev_image.hip``).
 
 ``overlay`` is a third tail (``csrc/overlay.hip``) for the picture a person looks at
 (``create_visualization``, ``kuruma/core/preprocessing.py:85-104``): the frame blended with the
@@ -302,6 +304,51 @@ class EndToEndFastSCNN(nn.Module):
                                         return_mask)
         object.__setattr__(self, "_last_fused", fused)
         return mask, rows
+
+    def bird_eye_view(self, frames, view_params, frame_view_params=None, scale=255, min_width=10,
+                      segmented=False, alpha=0.5, color=(0, 255, 0)):
+        """The colour bird's-eye view next to the mask: ``(bev_image, bev_mask, rows)``, plus the
+        segmented picture with ``segmented=True`` -- what ``transform_image_and_mask`` and
+        ``create_visualization(bird_eye_image, bird_eye_mask)`` give the reference
+        (``kuruma/core/inference.py:275-287``).
+
+        ``bev_mask`` and ``rows`` are ``bird_eye(frames, view_params, scale, min_width)``, same
+        bits and same routing.  ``bev_image`` is the uint8 frames warped bilinearly to the same view
+        (``bev.warp_image``, border 0, the layout and channel order of the frames), the segmented
+        picture that image with ``color`` (in the frames' channel order) blended at ``alpha`` where
+        the mask is set.  Both come from one more launch on the same stream (``csrc/bev_image.hip``);
+        nothing is read back.
+
+        ``view_params`` describes the mask's source, ``input_size``, as for ``bird_eye``.  Frames of
+        another size need their own matrix: pass ``frame_view_params`` = the same view built with
+        ``BirdEyeView.params(..., source_size=(w, h))``.  Float frames are refused by this method
+        only: the law is OpenCV's fixed-point remap of 8-bit images."""
+        who = "EndToEndFastSCNN.bird_eye_view"
+        if isinstance(frames, torch.Tensor) and frames.dtype != torch.uint8:
+            raise RuntimeError("%s: frames are uint8, not %s: a float frame would take OpenCV's "
+                               "float bilinear law, which this is not" % (who, frames.dtype))
+        if not isinstance(frames, torch.Tensor) or frames.dim() != 4:
+            raise RuntimeError("%s: expected 4-d frames" % who)
+        wb, hb = (int(v) for v in view_params["output_size"])
+        h, w = (int(v) for v in (frames.shape[1:3] if self.channels_last else frames.shape[2:4]))
+        wo, ho = int(self.input_size[0]), int(self.input_size[1])
+        if frame_view_params is None:
+            if (w, h) != (wo, ho):
+                raise RuntimeError(
+                    "%s: the frames are %d x %d but view_params maps input_size %d x %d; pass "
+                    "frame_view_params=BirdEyeView.params(pixels_per_unit, margin_ratio, "
+                    "full_image, source_size=(%d, %d))[3] for the same view"
+                    % (who, w, h, wo, ho, w, h))
+            frame_view_params = view_params
+        elif tuple(int(v) for v in frame_view_params["output_size"]) != (wb, hb):
+            raise RuntimeError("%s: frame_view_params has output_size %s but view_params %s; both "
+                               "describe one view" % (who, tuple(frame_view_params["output_size"]),
+                                                      (wb, hb)))
+        mask, rows = self.bird_eye(frames, view_params, scale=scale, min_width=min_width)
+        res = _bev.warp_image(frames, _bev.inverse_map(frame_view_params), (wb, hb),
+                              channels_last=bool(self.channels_last),
+                              mask=mask if segmented else None, alpha=alpha, color=color)
+        return (res[0], mask, rows, res[1]) if segmented else (res, mask, rows)
 
     # ---- the steering tail ------------------------------------------------------------------------
     def steer(self, frames, view_params, controller=None, smooth_method="polynomial", degree=3,

@@ -283,6 +283,45 @@ int fscnn_forward_e2e_overlay(const fscnn_plan* plan, const void* x, int x_dtype
                               float frame_weight, float alpha, float gamma, unsigned char* out,
                               unsigned char* mask_out, const float* params, float* running,
                               long long* nbt, void* ws, void* stream);
+/* Colour bird's-eye view of the deployment pipeline: the other half of
+ * PerspectiveTransformer.transform_image_and_mask (kuruma/vision/transform.py:174-180) -- the
+ * camera frame warped to the bird's-eye view with cv2.INTER_LINEAR and a constant 0 border -- and,
+ * in the same launch, the segmented bird's-eye picture (create_visualization of the warped frame
+ * and the warped mask, kuruma/core/inference.py:275-287).  One workgroup per 256 pixels of a view
+ * row.
+ *
+ * The law is the shape of OpenCV's fixed-point bilinear remap for 8-bit images as warpPerspective
+ * drives it: 5 fractional coordinate bits, product weights.  Bit parity with a particular OpenCV
+ * build is not claimed; the law below is what is tested.
+ * m[9]: HOST doubles, destination -> source as for fscnn_bev_mask, all finite, otherwise -1.  For
+ * view pixel (x, y), in fp64, every operation rounded on its own (no fused multiply-add):
+ *     X = (m0*x + m1*y) + m2      Y = (m3*x + m4*y) + m5      W = (m6*x + m7*y) + m8
+ *     W = (W != 0) ? 32.0 / W : 0
+ *     fx = rint(max(INT_MIN, min(INT_MAX, X*W)))  (a NaN product counts as INT_MAX; half to even)
+ *     sx = fx >> 5 (arithmetic), ax = fx & 31;  fy, sy, ay the same from Y
+ * The four taps are p00 = (sx, sy), p10 = (sx+1, sy), p01 = (sx, sy+1), p11 = (sx+1, sy+1); a tap
+ * outside 0 <= . < w, 0 <= . < h contributes 0, each tap on its own.  Per channel, in integers:
+ *     S   = (32-ax)(32-ay)*p00 + ax(32-ay)*p10 + (32-ax)ay*p01 + ax*ay*p11
+ *     out = (S + 512) >> 10
+ * (the same integer as a 15-bit weight table with + 2^14 >> 15: product weights of 5-bit fractions
+ * are exact multiples of 32).  Exact, deterministic, no atomics.
+ *
+ * frames: uint8 only, [N][h][w][3] with channels_last != 0, else [N][3][h][w]; channels are never
+ * swapped.  image: the warped frames, uint8 in the layout of the frames ([N][Hb][Wb][3] or
+ * [N][3][Hb][Wb]).  blended: the overlay law's lane mode and blend above applied to the warped
+ * byte a: o_k = color[k] (HOST uint8[3], in the frames' channel order) where the byte of bev_mask
+ * (uint8 [N][Hb][Wb], e.g. fscnn_bev_mask's) is not 0, else 0;
+ * t = ((a * frame_weight) + (o_k * alpha)) + gamma in fp32, out = uint8(min(max(rint(t), 0), 255)),
+ * NaN -> 0 (the same device function).  image and blended may each be null, not both (-1);
+ * blended needs bev_mask and color (-1).  The outputs are buffers of their own: aliasing the
+ * frames, the mask or each other is refused (-1).
+ * Limits: 1 <= N <= 65535, 1 <= Wb <= 8192, 1 <= Hb <= 65535, 2 <= h, w <= 16384.  Outside them:
+ * -2, nothing launched. */
+int fscnn_bev_image(const unsigned char* frames, int channels_last, int N, int h, int w,
+                    const double* m, int Hb, int Wb, unsigned char* image,
+                    const unsigned char* bev_mask, const unsigned char* color /* HOST[3] */,
+                    float frame_weight, float alpha, float gamma, unsigned char* blended,
+                    void* stream);
 /* Steering tail of the deployment pipeline: from the row table of the bird's-eye tail to the two
  * wheel commands, what the reference does on the host with PathPlanner.smooth_path /
  * generate_waypoints / plan_complete_path / _calculate_path_length
